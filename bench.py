@@ -20,16 +20,29 @@ ceil(K/2) iterations) are reported beside it, never as `value`.
 
 Prints ONE JSON line (rank 0): metric/value/unit for the headline config,
 its roofline (the assignment call -- the dominant kernels -- timed with HIP
-events on its stream over the timed fit, and over its steady iterations),
-a CPU baseline (the oracle on this host, rank 0, N=1 only, bounded sample),
-the fit_predict variant (labels written), per-iteration wall and kernel
-times, and under "extra_configs" the other single-GPU BASELINE configs
-measured the same way in the same run: configs[0] (C1), configs[2]'s
-per-GPU shard (125M x 64, k=1000, the north-star target), configs[3] (10M
-x 1024, k=4096, fp64 and fp32; MFMA) and configs[4] (CSR 10M x 10k, 10
-entries per row, k=256: fit and predict).
+events on its stream over the timed fit, and over its steady iterations)
+and per-iteration wall and kernel times.  A plain run does only that: data,
+warmup, the K timed steps, the result line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--only-headline]
+--full adds the measurements that take runs of their own: a CPU baseline
+(the oracle on this host, rank 0, N=1 only, bounded sample), the
+fit_predict variant (labels written), and under "extra_configs" the other
+single-GPU BASELINE configs measured the same way in the same run:
+configs[0] (C1), configs[2]'s per-GPU shard (125M x 64, k=1000, the
+north-star target), configs[3] (10M x 1024, k=4096, fp64 and fp32; MFMA)
+and configs[4] (CSR 10M x 10k, 10 entries per row, k=256: fit and predict).
+--only-headline and --no-cpu trim a --full run.
+
+--dump-outputs DIR writes what the timed fit returned after its last step
+as DIR/<name>.npy (float64): `centers` (k x d), and with --labels the
+labels of a fixed seeded sample of rows (`labels_sample`, at
+`labels_sample_index`).  The data and the initial centres are seeded, so
+two builds run with the same arguments can be compared array for array:
+labels are bit-identical from run to run, centres agree to ~1e-14 relative
+(the order of the fp64 atomic sums is not fixed).
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--only-headline] [--no-cpu]
   torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -63,10 +76,16 @@ def parse():
     p.add_argument("--mode", default="auto")
     p.add_argument("--labels", action="store_true",
                    help="headline = fit_predict (labels written)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the CPU baselines, the fit_predict variant "
+                        "and the extra configs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the timed fit's outputs after its last step "
+                        "as DIR/<name>.npy")
     p.add_argument("--only-headline", action="store_true",
-                   help="skip the fit_predict and extra-config runs")
+                   help="--full: skip the fit_predict and extra-config runs")
     p.add_argument("--no-cpu", action="store_true",
-                   help="skip the CPU baselines")
+                   help="--full: skip the CPU baselines")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--extras-scale", type=float, default=1.0,
                    help="scale the extra configs' rows per GPU (rehearsals "
@@ -77,7 +96,10 @@ def parse():
     p.add_argument("--traffic-json", default=None,
                    help="PMC traffic summary for the headline (default: "
                         "profiles/traffic/d<d>_k<k>.json when present)")
-    return p.parse_args()
+    a = p.parse_args()
+    if not a.full:              # a plain run: the headline's timed fit only
+        a.only_headline = a.no_cpu = True
+    return a
 
 
 # ---------------------------------------------------------------------------
@@ -196,7 +218,8 @@ def _cpu_task(block, centers, sparse=False):
 # one configuration on the GPU(s)
 # ---------------------------------------------------------------------------
 def run_config(torch, dist, dev, rank, world, n, d, k, subset, steps, warmup,
-               mode, labels, n_blobs=None, f32=False, csr_nnz=0, host_x=None):
+               mode, labels, n_blobs=None, f32=False, csr_nnz=0, host_x=None,
+               dump=False):
     """One configuration, timed as SURVEY 8(d) defines the metric: the wall
     time of a whole Lloyd loop, from after the data is resident and the
     centres are initialised through the last convergence decision.
@@ -325,9 +348,35 @@ def run_config(torch, dist, dev, rank, world, n, d, k, subset, steps, warmup,
            "counters": st.screened_blocks() if not csr_nnz and
            getattr(st, "sorting", False) else None,
            "nkb": (k + 31) // 32}
+    if dump:
+        out["outputs"] = fit_outputs(torch, st, labels)
     del st, ds, X, dd
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_LABELS = 1 << 20          # rows of the --dump-outputs label sample
+
+
+def fit_outputs(torch, st, labels):
+    """What the timed fit hands its caller after the last step (KMeans._do_fit
+    after the loop): the centres, and for fit_predict the labels of the last
+    assignment -- of a fixed seeded sample of this rank's rows, 8 MB each for
+    labels and row indices whatever n is."""
+    out = {"centers": st.centers_host().astype(np.float64)}
+    if labels and st.dd.n > 0:
+        idx = np.sort(np.random.default_rng(0).integers(
+            0, st.dd.n, min(st.dd.n, DUMP_LABELS)))
+        lab = st.labels[:st.dd.n][torch.from_numpy(idx).to(st.labels.device)]
+        out["labels_sample_index"] = idx.astype(np.float64)
+        out["labels_sample"] = lab.cpu().numpy().astype(np.float64)
+    return out
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def traffic_for(n, d, k, path=None, csr_nnz=0):
@@ -593,8 +642,11 @@ def main():
             raise SystemExit(3)
 
     r = run_config(torch, dist, dev, rank, world, a.n, a.d, a.k, a.subset,
-                   a.steps, a.warmup, a.mode, a.labels)
+                   a.steps, a.warmup, a.mode, a.labels,
+                   dump=bool(a.dump_outputs) and rank == 0)
     check_collective(r)
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, r.pop("outputs"))
     fp = None
     if not a.only_headline and not a.labels:
         fp = run_config(torch, dist, dev, rank, world, a.n, a.d, a.k,

@@ -22,6 +22,6 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 if [ $# -gt 0 ]; then
   bash tools/ab_libs.sh $TAG main "$@" || exit $?
 fi
-step bench 400 python bench.py --steps 20 --warmup 3
-step prof 400 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/${TAG}_prof -o run -- python bench.py --steps 10 --warmup 2 --no-cpu
+step bench 400 python bench.py --full --steps 20 --warmup 3
+step prof 400 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/${TAG}_prof -o run -- python bench.py --full --steps 10 --warmup 2 --no-cpu
 echo "== done"
