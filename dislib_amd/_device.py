@@ -341,6 +341,62 @@ def assign_delta(dd, C, ws, labels, delta, mode, image=None):
                "dkm_assign_delta")
 
 
+def bounds_ok(dd, k, mode, ws):
+    """Can a fit of (k, d, mode) on ``dd`` keep per-row distance bounds
+    (dkm_assign_delta_bounds_*)?  The shapes of the d <= 32 hinted screen in
+    auto / bf16x3 mode, a workspace with n label slots and the sample image
+    enabled."""
+    if dd.sparse or dd.n == 0 or not X_IMAGE or dd.n >= 2 ** 31:
+        return False
+    if mode not in (_lib.MODE_AUTO, _lib.MODE_BF16X3):
+        return False
+    so = _lib.lib()
+    if not so.dkm_bounds_ok(int(k), dd.d):
+        return False
+    if int(so.dkm_x_image_kind(int(k), dd.d, int(mode))) != _lib.IMAGE_SPLIT:
+        return False
+    return int(so.dkm_workspace_bytes(int(k), dd.d, dd.n)) <= ws.nbytes
+
+
+def alloc_bounds(dd):
+    """The fit's (ub, lb): two fp32 arrays of n entries, or None when they
+    would leave less than 4 GiB of HBM free (the image's rule)."""
+    t = torch()
+    nb = 8 * dd.n
+    free = t.cuda.mem_get_info(dd.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        return None
+    # (rows padded to 64 entries: both arrays start 16-B aligned)
+    npad = (dd.n + 63) // 64 * 64
+    return _alloc("bounds", 8 * npad, lambda: t.empty(
+        (2, npad), dtype=t.float32, device=dd.device))
+
+
+def assign_delta_bounds(dd, C, ws, labels, delta, mode, image, bounds, init):
+    """assign_delta with per-row bounds: ``bounds`` = the (2, >= n) fp32 tensor
+    of alloc_bounds, ``init`` = it holds nothing valid for ``labels``."""
+    so = _lib.lib()
+    img, kind = image
+    fn = so.dkm_assign_delta_bounds_f32 if dd.dtype == np.float32 else \
+        so.dkm_assign_delta_bounds_f64
+    _lib.check(fn(ptr(dd.X), ptr(img), kind, img.numel(), dd.n, dd.d,
+                  dd.X.stride(0), ptr(C), C.shape[0], ws.p, ws.nbytes,
+                  ptr(labels), ptr(delta), mode, ptr(bounds[0]),
+                  ptr(bounds[1]), _lib.BOUNDS_INIT if init else 0,
+                  stream_ptr()), "dkm_assign_delta_bounds")
+
+
+def bounds_counters(ws):
+    """(calls that ran the bounds pass, rows it left active, rows it
+    skipped, calls that screened the active rows as a list) over the
+    workspace's life (dkm_bounds_counters)."""
+    so = _lib.lib()
+    out = (ctypes.c_int64 * 4)()
+    _lib.check(so.dkm_bounds_counters(ws.p, out, stream_ptr()),
+               "dkm_bounds_counters")
+    return tuple(int(x) for x in out)
+
+
 def sorted_image_ok(dd, k):
     """Does the fit's auto mode on (k, d) run the single-product screen that
     takes a label-sorted image (dkm_x_image_sorted_ok)?"""

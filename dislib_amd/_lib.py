@@ -11,13 +11,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DKM_LIB", os.path.join(_HERE, "libdkm.so"))
 
 # constants mirrored from include/dkm.h
-ABI_VERSION = 3
+ABI_VERSION = 4
 MODE_AUTO, MODE_EXACT, MODE_SCREEN32, MODE_BF16X3, MODE_BF16 = 0, 1, 2, 3, 4
 MODE_MASK, MODE_NOHINT, MODE_B1, MODE_TRANSLATE = 0xff, 0x100, 0x200, 0x400
 IMAGE_NONE, IMAGE_SINGLE, IMAGE_SPLIT, IMAGE_SORTED, IMAGE_GEMM = 0, 1, 2, 3, 4
 IMAGE_BUILD = 0x100   # kind flag: build the allocated image during the call
 SUMS_F64, SUMS_F32, SUMS_RECIP = 0, 1, 2
 PREP_CSR = 1
+BOUNDS_INIT = 1
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -63,6 +64,14 @@ SIGNATURES = {
                                         _p, _i64, _p, _sz, _p, _p, _i32, _p]),
     "dkm_assign_delta_img_f32": (_i32, [_p, _p, _i32, _sz, _i64, _i64, _i64,
                                         _p, _i64, _p, _sz, _p, _p, _i32, _p]),
+    "dkm_bounds_ok": (_i32, [_i64, _i64]),
+    "dkm_assign_delta_bounds_f64": (_i32, [_p, _p, _i32, _sz, _i64, _i64,
+                                           _i64, _p, _i64, _p, _sz, _p, _p,
+                                           _i32, _p, _p, _i32, _p]),
+    "dkm_assign_delta_bounds_f32": (_i32, [_p, _p, _i32, _sz, _i64, _i64,
+                                           _i64, _p, _i64, _p, _sz, _p, _p,
+                                           _i32, _p, _p, _i32, _p]),
+    "dkm_bounds_counters": (_i32, [_p, ctypes.POINTER(_i64), _p]),
     "dkm_label_sums_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,
                                   _p, _p]),
     "dkm_label_sums_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,

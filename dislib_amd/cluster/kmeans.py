@@ -26,6 +26,8 @@ tree).  Extra keyword-only arguments select the assignment arithmetic
 (``mode``: "auto" | "exact" | "screen32" | "bf16x3" | "bf16", identical
 labels) and the device.
 """
+import os
+
 import numpy as np
 from scipy.sparse import csr_matrix, issparse
 
@@ -172,6 +174,12 @@ SORT_AT = 1
 # (profiles/r06/c3/r06h_translate_iters.txt).  Labels are identical either
 # way; the tests run both.
 TRANSLATE_FIRST = False
+# Per-row distance bounds (Hamerly's pair, dkm_assign_delta_bounds_*,
+# DESIGN.md 3.14) in the d <= 32 fits: a row whose upper bound to its own
+# centre is below its lower bound to every other keeps its label unread.
+# Labels are identical without them (DKM_BOUNDS=0, or this attribute, turns
+# them off: the tests and A/B runs).
+BOUNDS = os.environ.get("DKM_BOUNDS", "1") != "0"
 
 
 class _Lloyd:
@@ -240,6 +248,12 @@ class _Lloyd:
         self.sorting = (SORTED_IMAGE and mode == "auto" and
                         sorted_image_ok(dd, k))
         self.simg = None          # (tensor, IMAGE_SORTED) once built
+        # per-row bounds: allocated at the first hinted image iteration
+        from .._device import bounds_ok
+        self.bounding = (BOUNDS and not self.sorting and
+                         bounds_ok(dd, k, self.mode, self.ws))
+        self.bounds = None        # (2, n) fp32 once allocated
+        self.bounds_valid = False  # they hold for self.labels
 
     def prepare(self):
         """Per-iteration centre data + zeroed accumulator."""
@@ -313,9 +327,35 @@ class _Lloyd:
             if self._full():
                 partial_sum(self.dd, self.C, self.ws, self.labels, self.acc,
                             mode, image=image)
+                self.bounds_valid = False
+                return
+            bimg = self._bounds_image()
+            if bimg is not None:
+                from .._device import assign_delta_bounds
+                assign_delta_bounds(self.dd, self.C, self.ws, self.labels,
+                                    self.acc, mode, bimg, self.bounds,
+                                    not self.bounds_valid)
+                self.bounds_valid = True
             else:
                 assign_delta(self.dd, self.C, self.ws, self.labels, self.acc,
                              mode, image=image)
+                self.bounds_valid = False
+
+    def _bounds_image(self):
+        """The built split image of a delta iteration that keeps bounds (they
+        are allocated here, at the first such iteration), else None."""
+        if not self.bounding:
+            return None
+        from .._device import alloc_bounds
+        img, kind = self.dd.screen_image(self.k, self.mode)
+        if img is None or kind != _lib.IMAGE_SPLIT:
+            return None          # no image, or not built yet
+        if self.bounds is None:
+            self.bounds = alloc_bounds(self.dd)
+            if self.bounds is None:
+                self.bounding = False      # HBM is short: today's path
+                return None
+        return img, kind
 
     def assign(self):
         self.prepare()
@@ -362,6 +402,12 @@ class _Lloyd:
         from .._device import screen_counters
         with self._on():
             return screen_counters(self.ws)
+
+    def bounds_counters(self):
+        """(bounds passes, rows active, rows skipped, list screens) so far."""
+        from .._device import bounds_counters
+        with self._on():
+            return bounds_counters(self.ws)
 
     def rechecked(self):
         from .._device import rechecked

@@ -1094,16 +1094,61 @@ __device__ __forceinline__ void wave_sync_w() {
 // score: about 0.6 VALU instead of the top-2's 3 (VALU:MFMA 13:1, the
 // limit of this kernel, round-5 PMC).  The decision over {p} and the kept
 // scores is the same rule, exactly: every centre left out is > T.
-constexpr int W32_HINT_KMAX = 256;
-template <class TX, bool IMG, bool HINT = false>
+// (W32_HINT_KMAX: dkm_internal.h)
+//
+// BND (hinted delta launches with per-row bounds): every
+// row the pass decides gets u >= |x - c_label| and l <= the distance to
+// every other centre, from its own score, the least score of the others
+// (a running minimum of the threshold pass's per-block minima; p's slot is
+// poisoned, so it leaves p out) and the screen's bound B; a row left to the
+// re-check gets (+inf, 0).  With IMG the pass is the image screen over all
+// rows; without, its list form: the wave's 32 rows are list[32 t + r] (the
+// rows the bounds pass left active), read and converted from X, and every
+// per-row result goes back to that row.  In an update call (bnd.upd) the
+// two are launched one after the other and the device count of active rows
+// picks the one that runs: the other returns at once.
+struct BoundsHost {  // dkm_assign_delta_bounds_*: the caller's arrays
+  float *ub, *lb;
+  int init;  // they hold nothing yet: the image screen writes them
+};
+struct BndArgs {
+  float *ub, *lb;
+  const int32_t *list;    // active rows (list form)
+  const uint32_t *nact;   // their number (device)
+  uint32_t thresh;        // list form iff *nact <= thresh
+  int upd;                // 0: the image screen runs whatever *nact
+  int vec;                // list form: rows are read in 16-B pieces (else
+                          // element by element: d % 8 != 0 or unaligned X)
+};
+template <class TX, bool IMG, bool HINT = false, bool BND = false>
 __global__ void __launch_bounds__(SBW) __attribute__((
     amdgpu_waves_per_eu(DKM_W32_WPE)))
     k_screen_w32(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
                  int k, WsView v, int32_t *__restrict__ lab_out, double *acc,
                  int amode, int64_t base, int use_list, XImage img,
-                 int build) {
+                 int build, BndArgs bnd = BndArgs{}) {
   constexpr int GB = 8;  // 32-centre blocks per packing group
+  constexpr bool LIST = BND && !IMG;
+  static_assert(!BND || HINT, "bounds come from the threshold pass");
   extern __shared__ __attribute__((aligned(16))) double smem[];
+  int64_t nl = n;  // rows to walk: n, or the list's length
+  if constexpr (BND) {
+    const uint32_t na = bnd.upd ? *bnd.nact : 0u;
+    const bool listpath = bnd.upd && na <= bnd.thresh;
+    if constexpr (LIST) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        WsHeader *hd = v.hdr;
+        hd->bnd_calls += 1;
+        hd->bnd_active += na;
+        hd->bnd_skipped += (uint64_t)n - na;
+        hd->bnd_list_calls += listpath ? 1 : 0;
+      }
+      if (!listpath) return;
+      nl = na;
+    } else {
+      if (listpath) return;
+    }
+  }
   const int nkb = (int)(kpad32(k) / 32);
   char *frag = (char *)smem;                          // nkb x 4 KB
   float *cn = (float *)(frag + (int64_t)nkb * 4096);  // nkb x 32
@@ -1128,7 +1173,8 @@ __global__ void __launch_bounds__(SBW) __attribute__((
   // HINT: centre p's norm chunk (the 16 norms of its block half) with p's
   // own slot +2^100, 16 floats per centre, in place of the waves' scratch
   // (the image launches use none)
-  float *pcn = (float *)scr0;
+  // (the list form converts X: its norms follow the waves' scratch)
+  float *pcn = (float *)(scr0 + (IMG ? 0 : (SBW / 64) * W32_SCR));
   if constexpr (HINT) {
     for (int e = threadIdx.x; e < k * 16; e += SBW) {
       const int p = e >> 4, g = e & 15, q = p & 31;
@@ -1193,7 +1239,33 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     lane_off[i] = (uint32_t)((RI * i + lrow) * ldx * (int64_t)sizeof(TX)) +
                   (uint32_t)(16 * lpos);
   const bool two = d > 16;  // the second half holds features
+  int rowid = -1;  // LIST: the sample of this lane's row r (-1 past the list)
   auto load_tile = [&](int64_t s0) {
+    if constexpr (LIST) {
+      // rows list[s0 ..]: 64-bit addresses (no common base), and only the
+      // pieces that hold features (past d a piece could leave X)
+      rowid = s0 + r < nl ? bnd.list[s0 + r] : -1;
+      pv = rowid >= 0 ? lab_out[rowid] : -1;
+#pragma unroll
+      for (int i = 0; i < IC; ++i) {
+        const int64_t pos = s0 + RI * i + lrow;
+        const int64_t ro = pos < nl ? (int64_t)bnd.list[pos] : -1;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          raw[c][i] = txv{};
+          const int t0 = 16 * c + EPL * lpos;
+          if (ro < 0 || t0 >= d) continue;
+          if (bnd.vec) {
+            raw[c][i] = *(const txv *)(X + ro * ldx + t0);
+          } else {
+#pragma unroll
+            for (int e = 0; e < EPL; ++e)
+              if (t0 + e < d) raw[c][i][e] = X[ro * ldx + t0 + e];
+          }
+        }
+      }
+      return;
+    }
     const int64_t rows = std::max<int64_t>(0, n - s0);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
         (void *)(X + std::min(s0, n) * ldx), 0,
@@ -1244,16 +1316,17 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     }
   };
   int64_t s0 = base + wv * 32;
-  if (s0 < n) {
+  if (s0 < nl) {
     if constexpr (IMG)
       load_img(s0);
     else
       load_tile(s0);
   }
-  for (; s0 < n; s0 += step) {
+  for (; s0 < nl; s0 += step) {
     bf16x8 xh[2], xl[2];
     float xx;
     int prv;
+    const int crow = rowid;  // (before the next tile's prefetch)
     const int64_t s_next = s0 + step;
     if constexpr (IMG) {
       xh[0] = qi[0];
@@ -1262,7 +1335,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
       xl[1] = qi[3];
       xx = qxx;
       prv = qpv;
-      if (s_next < n) load_img(s_next);
+      if (s_next < nl) load_img(s_next);
     } else {
     float xp[IC];
 #pragma unroll
@@ -1330,7 +1403,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
       dst[192] = xl[1];
       if (h == 0) ((float *)img.xx)[s0 + r] = xx;
     }
-    if (!full_acc && s_next < n) load_tile(s_next);
+    if (!full_acc && s_next < nl) load_tile(s_next);
     }  // !IMG
 
     float r1 = INFINITY, r2 = INFINITY;
@@ -1342,6 +1415,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     // operands, the two halves added), T
     const int p = prv;
     const bool pok = HINT && p >= 0 && p < k;
+    float omin = INFINITY;  // BND: the least score of the centres but p
     float shp = INFINITY, T = INFINITY;
     if constexpr (HINT) {
       float dg = 0.f;
@@ -1398,7 +1472,9 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     if constexpr (HINT) {
       // the threshold pass: a block with no score <= T is done in 8 VALU
       auto test = [&](int cb, const f32x16 &accv) {
-        const bool hit = min16(accv, ninf) <= T;
+        const float m16 = min16(accv, ninf);
+        if constexpr (BND) omin = min_nc(omin, m16, ninf);
+        const bool hit = m16 <= T;
         if (__ballot(hit) == 0) return;
         if (hit) {
           float b1 = INFINITY, b2 = INFINITY;
@@ -1477,10 +1553,36 @@ __global__ void __launch_bounds__(SBW) __attribute__((
       ri = tk ? p : ri;
       r1 = tk ? shp : r1;
     }
-    const int64_t si = s0 + r;
+    const int64_t si = LIST ? (int64_t)crow : s0 + r;
+    const bool inr = LIST ? crow >= 0 : si < n;  // a row of this tile
     const bool sane = (xn < 1e18f) & (xn * cm < 1e30f) & (r1 < 1e30f);
     const bool unique = sane & (r2 - r1 > B2);
-    const bool und = si < n && !unique;
+    const bool und = inr && !unique;
+    if constexpr (BND) {
+      // the decided row's bounds under these centres.  Every score is
+      // within B = B2 / 2 of |c|^2 - 2 x.c, and xx within 2^-19 of |x|^2
+      // (d <= 32 fp32 terms): u^2 <= xx (1 + 2^-16) + r1 + B, and every
+      // other centre's distance^2 >= xx (1 - 2^-16) + so - B with so the
+      // least score but the label's: omin when the label stays p, else r2
+      // (p's score was kept, so every score left out exceeds T > r2).
+      // 1.01 B, the slack on xx and 2^-21 on the roots cover the fp32
+      // evaluation (B >= 2^-14 of every term's magnitude).
+      float oa, ob;
+      pair_xor<32>(omin, oa, ob);
+      omin = min_nc(oa, ob, ninf);
+      const float Bs = 0.505f * B2;
+      const float so = (pok && ri == p) ? omin : r2;
+      const float u2 = fmaf(xx, 1.0f + 0x1.0p-16f, r1 + Bs);
+      const float l2 = fmaf(xx, 1.0f - 0x1.0p-16f, so - Bs);
+      const float bu = __builtin_amdgcn_sqrtf(fmaxf(u2, 0.f)) *
+                       (1.0f + 0x1.0p-21f);
+      const float bl = __builtin_amdgcn_sqrtf(fmaxf(l2, 0.f)) *
+                       (1.0f - 0x1.0p-21f);
+      if (h == 0 && inr) {
+        bnd.ub[si] = unique ? bu : INFINITY;
+        bnd.lb[si] = unique ? bl : 0.f;
+      }
+    }
     const int prev = delta ? prv : -1;
     const uint64_t um = __ballot(h == 0 && und);
     const int add = __popcll(um);
@@ -1494,7 +1596,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     }
     if (!IMG && full_acc) {
       // the loading lanes add their pieces of the decided rows
-      if (h == 0) s_lab[r] = si < n && unique ? ri : -1;
+      if (h == 0) s_lab[r] = inr && unique ? ri : -1;
       wave_sync_w();
 #pragma unroll
       for (int i = 0; i < IC; ++i) {
@@ -1512,7 +1614,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
         }
       }
     }
-    if (si < n) {
+    if (inr) {
       const int lab = ri;
       if (h == 0 && !(unique && lab == prev))
         lab_out[si] = unique ? lab : -(prev + 2);
@@ -1541,7 +1643,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
     }
     if (mlist) {
       // a row the screen moved: listed with its previous label
-      const bool mv = h == 0 && si < n && unique && ri != prev;
+      const bool mv = h == 0 && inr && unique && ri != prev;
       const uint64_t mm = __ballot(mv);
       if (mm) {
         const int c = __popcll(mm);
@@ -1553,7 +1655,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
         mcnt += c;
       }
     }
-    if (!IMG && full_acc && s_next < n) load_tile(s_next);
+    if (!IMG && full_acc && s_next < nl) load_tile(s_next);
   }
   if (mlist && mcnt) mflush();
   if (lane == 0) {
@@ -3063,38 +3165,155 @@ static int launch_moved_sums(const TX *X, int64_t ldx, int d, int k,
   return check_launch("moved-row sums");
 }
 
+// The bounds pass: one stream over (ub, lb, label), four
+// rows per lane in 16-B loads.  u grows by the drift of the row's own centre
+// and l shrinks by the largest drift of any other (k_drift), each rounded
+// away from the other (the 2^-22 factors cover the fp32 add); a row with
+// !(u < l) -- ties, NaN and the re-checks' (+inf, 0) included -- is listed
+// for the screen.  Listing as AM_MLIST's: rows staged in LDS per wave, one
+// reservation per BP_STAGE rows.  Past `cap` entries the rows are only
+// counted (the image screen then takes every row).
+constexpr int BP_STAGE = 1024;
+__global__ void __launch_bounds__(256)
+    k_bounds_pass(float *__restrict__ ub, float *__restrict__ lb,
+                  const int32_t *__restrict__ lab, int64_t n, int k, WsView v,
+                  int32_t *__restrict__ list, uint32_t cap) {
+  __shared__ int stage[4][BP_STAGE];
+  __shared__ float sdr[W32_HINT_KMAX];
+  for (int e = threadIdx.x; e < k; e += 256) sdr[e] = v.drift[e];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int *st = stage[wid];
+  const float d1 = v.hdr->dmax1, d2 = v.hdr->dmax2;
+  const int im = v.hdr->dimax;
+  const bool bad = v.hdr->drift_bad != 0;
+  int cnt = 0;  // wave-uniform
+  auto flush = [&]() {
+    wave_sync_w();
+    uint32_t at0 = 0;
+    if (lane == 0) at0 = atomicAdd(&v.hdr->nactive, (uint32_t)cnt);
+    at0 = (uint32_t)__shfl((int)at0, 0, 64);
+    for (int e = lane; e < cnt; e += 64)
+      if (at0 + (uint32_t)e < cap) list[at0 + e] = st[e];
+    wave_sync_w();
+    cnt = 0;
+  };
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t b0 = ((int64_t)blockIdx.x * 4 + wid) * 256; b0 < n;
+       b0 += nw * 256) {
+    if (cnt + 256 > BP_STAGE) flush();
+    const int64_t i0 = b0 + 4 * lane;
+    float u[4], l[4];
+    int lbv[4];
+    const bool whole = i0 + 3 < n;
+    if (whole) {
+      const f32x4 u4 = *(const f32x4 *)(ub + i0);
+      const f32x4 l4 = *(const f32x4 *)(lb + i0);
+      const int4 q4 = *(const int4 *)(lab + i0);
+      u[0] = u4.x; u[1] = u4.y; u[2] = u4.z; u[3] = u4.w;
+      l[0] = l4.x; l[1] = l4.y; l[2] = l4.z; l[3] = l4.w;
+      lbv[0] = q4.x; lbv[1] = q4.y; lbv[2] = q4.z; lbv[3] = q4.w;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const bool in = i0 + c < n;
+        u[c] = in ? ub[i0 + c] : 0.f;
+        l[c] = in ? lb[i0 + c] : 1.f;
+        lbv[c] = in ? lab[i0 + c] : 0;
+      }
+    }
+    bool act[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const bool ok = !bad && lbv[c] >= 0 && lbv[c] < k;
+      const float down = lbv[c] == im ? d2 : d1;
+      u[c] = ok ? (u[c] + sdr[ok ? lbv[c] : 0]) * (1.0f + 0x1.0p-22f)
+                : INFINITY;
+      l[c] = fmaxf(l[c] - down, 0.f) * (1.0f - 0x1.0p-22f);
+      act[c] = i0 + c < n && !(u[c] < l[c]);
+    }
+    if (whole) {
+      *(f32x4 *)(ub + i0) = f32x4{u[0], u[1], u[2], u[3]};
+      *(f32x4 *)(lb + i0) = f32x4{l[0], l[1], l[2], l[3]};
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (i0 + c < n) {
+          ub[i0 + c] = u[c];
+          lb[i0 + c] = l[c];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const uint64_t m = __ballot(act[c]);
+      if (act[c]) st[cnt + lane_prefix(m)] = (int)(i0 + c);
+      cnt += __popcll(m);
+    }
+  }
+  if (cnt) flush();
+}
+
+// BOUNDS_LIST_FRAC, or DKM_BOUNDS_LIST_FRAC from the environment (read at
+// every call: a tuning run changes it between fits)
+static double bounds_list_frac() {
+  const char *e = getenv("DKM_BOUNDS_LIST_FRAC");
+  if (!e || !*e) return BOUNDS_LIST_FRAC;
+  char *end = nullptr;
+  const double f = strtod(e, &end);
+  return end == e ? BOUNDS_LIST_FRAC : f;
+}
+
 template <class TX>
 static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
                              int k, const WsView &v, int32_t *lab_out,
                              double *acc, int amode, int64_t base, size_t lds,
                              int use_list, hipStream_t s, int *nseg,
-                             XImage img, bool build = false) {
+                             XImage img, bool build = false,
+                             const BndArgs *bnd = nullptr,
+                             bool listform = false) {
   // the image serves launches that need no sums from the raw rows; a build
   // launch (full sums, base 0) writes it instead
   const bool im = !build && img.tiles && img.kind == IMG_SPLIT &&
-                  !am_full(amode) && base % 32 == 0;
+                  !am_full(amode) && base % 32 == 0 && !listform;
   // the waves' transpose scratch: the X-converting launches only (three
   // blocks per CU need <= 53 KB each)
   if (!im) lds += (size_t)(SBW / 64) * W32_SCR;
-  // the threshold pass: image delta launches (incoming labels = hints)
+  // the threshold pass: image delta launches (incoming labels = hints) and
+  // the bounds' list form
   const size_t pcn_bytes = (size_t)kpad32(k) * 16 * 4;
-  const bool hint = im && (amode & AM_DELTA) && k <= W32_HINT_KMAX &&
-                    lds + pcn_bytes <= LDS_BUDGET;
+  const bool hint = (im || listform) && (amode & AM_DELTA) &&
+                    k <= W32_HINT_KMAX && lds + pcn_bytes <= LDS_BUDGET;
   if (hint) lds += pcn_bytes;
   // AM_MLIST: the moved-row staging after them (the kernel's layout)
   if (amode & AM_MLIST) {
-    if (!(im && hint)) return 1;  // the image threshold pass only
+    if (!hint) return 1;  // the threshold passes only
     lds += (size_t)(SBW / 64) * W32_MLB * 4;
   }
-  const void *kf = hint ? (const void *)k_screen_w32<TX, true, true>
-                   : im ? (const void *)k_screen_w32<TX, true>
-                        : (const void *)k_screen_w32<TX, false>;
+  // bounds: the moved-row-listing threshold passes only
+  if (bnd && !(hint && (amode & AM_MLIST) && base == 0)) return 1;
+  const void *kf =
+      bnd    ? (listform ? (const void *)k_screen_w32<TX, false, true, true>
+                         : (const void *)k_screen_w32<TX, true, true, true>)
+      : hint ? (const void *)k_screen_w32<TX, true, true>
+      : im   ? (const void *)k_screen_w32<TX, true>
+             : (const void *)k_screen_w32<TX, false>;
   const int64_t cap = (int64_t)dev_info().cus * resident_blocks(kf, SBW, lds);
   const int64_t per_block = 32 * (SBW / 64);
-  const int64_t need = (end - base + per_block - 1) / per_block;
+  // (the list form's grid is sized for its longest list; the kernel reads
+  // the length on the device)
+  const int64_t rows = listform ? (int64_t)bnd->thresh : end - base;
+  const int64_t need = (rows + per_block - 1) / per_block;
   const unsigned g = (unsigned)std::max<int64_t>(1, std::min(need, cap));
   *nseg = (int)std::min<int64_t>((int64_t)g * (SBW / 64), TL_SEGS);
-  if (hint)
+  if (bnd && listform)
+    k_screen_w32<TX, false, true, true><<<g, SBW, lds, s>>>(
+        X, end, d, ldx, k, v, lab_out, acc, amode, base, use_list,
+        XImage{nullptr, nullptr, IMG_NONE}, 0, *bnd);
+  else if (bnd)
+    k_screen_w32<TX, true, true, true><<<g, SBW, lds, s>>>(
+        X, end, d, ldx, k, v, lab_out, acc, amode, base, use_list, img, 0,
+        *bnd);
+  else if (hint)
     k_screen_w32<TX, true, true><<<g, SBW, lds, s>>>(
         X, end, d, ldx, k, v, lab_out, acc, amode, base, use_list, img, 0);
   else if (im)
@@ -3528,7 +3747,8 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
                          int acc_kind, hipStream_t s, XImage img,
                          bool nohint = false, bool force_b1 = false,
                          void *build_img = nullptr, bool sub = false,
-                         bool transl = false);
+                         bool transl = false,
+                         const BoundsHost *bnds = nullptr);
 
 // The samples a screen left to the exact re-check (its per-wave lists) are
 // gathered, RS_ROWS at a time, and screened again by the chunked bf16x3
@@ -3598,7 +3818,7 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
                          size_t wsb, int32_t *labels, double *acc,
                          int acc_kind, hipStream_t s, XImage img,
                          bool nohint, bool force_b1, void *build_img,
-                         bool sub, bool transl) {
+                         bool sub, bool transl, const BoundsHost *bnds) {
   (void)wsb;
   const int64_t nq = std::min<int64_t>(v.nq, INT32_MAX);
   if (!labels && nq < 1)
@@ -3621,7 +3841,10 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
                            "screen (16-B aligned rows)");
   // d <= 32 bf16x3 with the 32x32x16 fragments resident: k_screen_w32
   const size_t fb32 = (size_t)(kpad32(k) / 32) * (4096 + 128);
-  const bool w32 = prec == P_B3 && d <= 32 && vec && fb32 <= LDS_BUDGET &&
+  // (a bounds call reads X only through the list form, which also takes
+  // rows that are not 16-B pieces: d % 8 != 0 or unaligned X)
+  const bool w32 = prec == P_B3 && d <= 32 && (vec || bnds) &&
+                   fb32 <= LDS_BUDGET &&
                    (int64_t)32 * ldx * (int64_t)sizeof(TX) < (1ll << 31) &&
                    !AB_NO_W32;
   const int chb = w32 ? 0 : screen_chunk_blocks(k, d);
@@ -3689,6 +3912,11 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
                (int64_t)n <= nq && sorted_sums_ok(k, n, v) && !AB_NO_MLIST;
   if (mlist && hipMemsetAsync(&v.hdr->nmoved, 0, 4, s) != hipSuccess)
     return fail(DKM_E_LAUNCH, "screen: memset");
+  // per-row bounds: the image threshold pass (with its moved-row list) only
+  if (bnds && !(mlist && v.prevc && bounds_shape(k, d)))
+    return fail(DKM_E_ARG, "bounds: the call does not take the d <= 32 "
+                           "image threshold pass (dkm_bounds_ok, a built "
+                           "split image, n label slots in the workspace)");
   for (int64_t base = 0; base < n; base += chunk) {
     const int64_t end = std::min(n, base + chunk);
     int32_t *lab_out = labels ? labels : v.queue - base;
@@ -3711,6 +3939,40 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
       r = launch_cand2<TX>(X, d, ldx, C, v, lab_out, base, nseg, s);
       if (!r && hint) r = launch_candn<TX>(X, d, ldx, C, v, lab_out, base,
                                            nseg, s);
+    } else if (w32 && bnds) {
+      // the bounds pass lists the rows with !(u < l) in v.sitems; then the
+      // list form and the image form of the screen, of which the device
+      // count of active rows lets one run (an init call: the image form)
+      const BndArgs ba{bnds->ub, bnds->lb, v.sitems, &v.hdr->nactive,
+                       (uint32_t)bounds_list_cap(n, bounds_list_frac()),
+                       bnds->init ? 0 : 1,
+                       vec ? 1 : 0};
+      int ns2 = 0;
+      r = 0;
+      if (ba.upd) {
+        if (hipMemsetAsync(&v.hdr->nactive, 0, 4, s) != hipSuccess ||
+            hipMemsetAsync(v.tcount, 0, (size_t)TL_SEGS * 4, s) != hipSuccess)
+          return fail(DKM_E_LAUNCH, "bounds: memset");
+        const unsigned gb = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((n + 1023) / 1024,
+                                 (int64_t)dev_info().cus * 8));
+        k_bounds_pass<<<gb, 256, 0, s>>>(bnds->ub, bnds->lb, lab_out, n, k, v,
+                                         v.sitems, ba.thresh);
+        if ((r = check_launch("bounds pass"))) return r;
+        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                  AM_DELTA | AM_MLIST, base, fb, use_list, s,
+                                  &ns2, img, false, &ba, true);
+      }
+      if (!r)
+        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                  AM_DELTA | AM_MLIST, base, fb, use_list, s,
+                                  &nseg, img, false, &ba, false);
+      if (r == 1) return fail(DKM_E_ARG, "bounds: the screens do not fit LDS");
+      nseg = std::max(nseg, ns2);
+      // the centres these bounds hold for: the next call's drift
+      if (!r && hipMemcpyAsync(v.prevc, C, (size_t)k * d * 8,
+                               hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(DKM_E_LAUNCH, "bounds: centre copy");
     } else if (w32) {
       r = mlist ? launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
                                         AM_DELTA | AM_MLIST, base, fb,
@@ -3837,7 +4099,7 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
                   const double *C, int64_t k, const void *ws, size_t wsb,
                   int32_t *labels, double *acc, int acc_kind, int mode,
                   void *stream, const char *who, const void *image = nullptr,
-                  int image_kind = 0) {
+                  int image_kind = 0, const BoundsHost *bnds = nullptr) {
   if (n < 0 || d <= 0 || k <= 0 || ldx < d)
     return fail(DKM_E_ARG, std::string(who) + ": bad n/d/k/ldx");
   if (d > INT32_MAX || k > INT32_MAX)
@@ -3892,6 +4154,10 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
                             x_image_bytes(n, d, image_kind), stream, who))
       return r;
   }
+  if (bnds && (mode != DKM_MODE_SCREEN_BF16X3 || !bounds_shape(k, d) ||
+               build || nohint))
+    return fail(DKM_E_ARG, std::string(who) + ": per-row bounds need the "
+                "hinted bf16x3 screen (AUTO or BF16X3, dkm_bounds_ok)");
   if (mode == DKM_MODE_EXACT)
     return launch_exact<TX>(X, n, (int)d, ldx, C, (int)k, labels, acc,
                             acc_kind, s);
@@ -3930,7 +4196,7 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
     return launch_screen<TX>(prec, X, n, (int)d, ldx, C, (int)k, v, wsb,
                              labels, acc, acc_kind, s, img, nohint, force_b1,
                              build && split_w32 ? (void *)image : nullptr,
-                             false, transl);
+                             false, transl, bnds);
   }
   return fail(DKM_E_ARG, std::string(who) + ": bad mode");
 }
@@ -4214,6 +4480,55 @@ int dkm_assign_delta_img_f32(const float *X, const void *image, int image_kind,
                        image_kind);
 }
 #undef DKM_IMG_CHECK
+
+static int bounds_args(float *ub, float *lb, const int32_t *labels,
+                       int flags, BoundsHost *b) {
+  if (!ub || !lb || !labels)
+    return fail(DKM_E_ARG, "assign_delta_bounds: NULL ub/lb/labels");
+  if (((uintptr_t)ub | (uintptr_t)lb | (uintptr_t)labels) % 16)
+    return fail(DKM_E_ARG, "assign_delta_bounds: ub, lb and labels must be "
+                           "16-B aligned");
+  if (flags & ~DKM_BOUNDS_INIT)
+    return fail(DKM_E_ARG, "assign_delta_bounds: unknown bounds flags");
+  *b = BoundsHost{ub, lb, (flags & DKM_BOUNDS_INIT) ? 1 : 0};
+  return 0;
+}
+
+int dkm_assign_delta_bounds_f64(const double *X, const void *image,
+                                int image_kind, size_t image_bytes, int64_t n,
+                                int64_t d, int64_t ldx, const double *C,
+                                int64_t k, const void *ws, size_t ws_bytes,
+                                int32_t *labels, double *delta, int mode,
+                                float *ub, float *lb, int bounds_flags,
+                                void *stream) {
+  if (!delta) return fail(DKM_E_ARG, "assign_delta_bounds: NULL delta");
+  if (n == 0) return 0;
+  BoundsHost b;
+  if (int r = bounds_args(ub, lb, labels, bounds_flags, &b)) return r;
+  if (!image || image_bytes < x_image_bytes(n, d, image_kind & ~DKM_IMAGE_BUILD))
+    return fail(DKM_E_ARG, "assign_delta_bounds: image missing or too small");
+  return assign<double>(X, n, d, ldx, C, k, ws, ws_bytes, labels, delta, 2,
+                        mode, stream, "dkm_assign_delta_bounds_f64", image,
+                        image_kind, &b);
+}
+
+int dkm_assign_delta_bounds_f32(const float *X, const void *image,
+                                int image_kind, size_t image_bytes, int64_t n,
+                                int64_t d, int64_t ldx, const double *C,
+                                int64_t k, const void *ws, size_t ws_bytes,
+                                int32_t *labels, double *delta, int mode,
+                                float *ub, float *lb, int bounds_flags,
+                                void *stream) {
+  if (!delta) return fail(DKM_E_ARG, "assign_delta_bounds: NULL delta");
+  if (n == 0) return 0;
+  BoundsHost b;
+  if (int r = bounds_args(ub, lb, labels, bounds_flags, &b)) return r;
+  if (!image || image_bytes < x_image_bytes(n, d, image_kind & ~DKM_IMAGE_BUILD))
+    return fail(DKM_E_ARG, "assign_delta_bounds: image missing or too small");
+  return assign<float>(X, n, d, ldx, C, k, ws, ws_bytes, labels, delta, 2,
+                       mode, stream, "dkm_assign_delta_bounds_f32", image,
+                       image_kind, &b);
+}
 
 int dkm_label_sums_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
                        const int32_t *labels, int64_t k, const void *ws,

@@ -78,8 +78,17 @@ struct WsHeader {
   int32_t pad3;
   uint64_t sfall_total;
   uint64_t umax_bits;  // max_c ||c - m||_2 (m: b1frag_t's translation)
+  // per-row distance bounds (dkm_assign_delta_bounds_*):
+  // the drift of the centres since the last bounds call (k_drift) ...
+  float dmax1, dmax2;   // largest / second-largest drift, rounded up
+  int32_t dimax;        // the centre that drifted most
+  uint32_t drift_bad;   // a drift was not finite: every row is active
+  uint32_t nactive;     // rows the bounds pass of this call left active
+  uint32_t pad4;
+  // ... and the counters of dkm_bounds_counters
+  uint64_t bnd_calls, bnd_active, bnd_skipped, bnd_list_calls;
 };
-constexpr uint64_t WS_MAGIC = 0x444b4d5753303035ull;  // "DKMWS005"
+constexpr uint64_t WS_MAGIC = 0x444b4d5753303036ull;  // "DKMWS006"
 constexpr size_t WS_HDR = 256;
 static_assert(sizeof(WsHeader) <= WS_HDR, "the header fits WS_HDR");
 
@@ -139,6 +148,27 @@ inline bool rescreen_ok(int64_t k, int64_t d) {
   return b1_ok(k, d) && d % 8 == 0 && d >= 8;
 }
 
+// Shapes whose steady iterations keep per-row distance bounds: where the
+// hinted image form of k_screen_w32 runs (d <= 32, k <= W32_HINT_KMAX); the
+// image holds any such d, and the list form reads rows that are not 16-B
+// pieces element by element
+constexpr int W32_HINT_KMAX = 256;
+inline bool bounds_shape(int64_t k, int64_t d) {
+  return d <= 32 && k >= 2 && k <= W32_HINT_KMAX;
+}
+// The bounds pass lists at most this share of the rows as active; with
+// more, the call screens every row from the image instead.  The default is
+// the measured crossover of the two paths (DESIGN.md 3.14,
+// tools/bounds_crossover.py); DKM_BOUNDS_LIST_FRAC in the environment
+// overrides it (0 = always the image form, 1 = always the list form: how
+// that tool times both paths at the same active share).
+constexpr double BOUNDS_LIST_FRAC = 0.45;
+inline int64_t bounds_list_cap(int64_t n, double frac) {
+  if (!(frac >= 0.0)) frac = 0.0;
+  if (frac > 1.0) frac = 1.0;
+  return (int64_t)((double)n * frac);
+}
+
 // GEMM screen eligibility: the register-tile screen takes d <= 128
 inline bool gemm_path(int64_t k, int64_t d) {
   return d > 128 && k >= 2 && k <= 32767;
@@ -173,6 +203,10 @@ struct WsView {
   uint16_t *b1frag_lo;
   float *mvec;
   float *cn32f;   // kpad32 ||c||^2 in 32x32 accumulator order
+  // bounds_shape(k, d) (else NULL): the centres of the last bounds call
+  // (k x d fp64) and each centre's drift since then (k fp32, rounded up)
+  double *prevc;
+  float *drift;
   uint16_t *b1frag; // b1_ok: bf16 hi of -2c, 32x32x16 order, dpad16 / 16
                     // K-steps per 32-centre block (k_screen_b1)
   int2 *clist;     // b1_ok: B1_SEGS x B1_CAP (offset, c1 | c2 << 16)

@@ -62,6 +62,10 @@ size_t ws_bytes(int64_t k, int64_t d, int64_t n_queue) {
   b += round_up(kpad16(k) * dpad32(d) * 4, 256);  // bfrag (hi + lo bf16)
   b += round_up(kpad32(k) * 32 * 4, 256);         // b32frag
   b += round_up(kpad32(k) * 4, 256);              // cn32f
+  if (bounds_shape(k, d)) {
+    b += round_up(k * d * 8, 256);                // prevc
+    b += round_up(k * 4, 256);                    // drift
+  }
   b += (size_t)TL_SEGS * TL_CAP * 8;  // tlist
   b += (size_t)TL_SEGS * 4;           // tcount
   if (mind_ok(k, d)) b += round_up(k * MIND_LD * 4, 256);  // mind
@@ -113,6 +117,14 @@ int ws_view(const void *ws, size_t bytes, int64_t k, int64_t d, WsView *v) {
   p += round_up(kpad32(k) * 32 * 4, 256);
   v->cn32f = (float *)p;
   p += round_up(kpad32(k) * 4, 256);
+  v->prevc = nullptr;
+  v->drift = nullptr;
+  if (bounds_shape(k, d)) {
+    v->prevc = (double *)p;
+    p += round_up(k * d * 8, 256);
+    v->drift = (float *)p;
+    p += round_up(k * 4, 256);
+  }
   v->tlist = (int2 *)p;
   p += (size_t)TL_SEGS * TL_CAP * 8;
   v->tcount = (int32_t *)p;
@@ -445,6 +457,51 @@ __global__ void __launch_bounds__(256) k_mind(const double *__restrict__ C,
     mind[p * MIND_LD + cb] = INFINITY;
 }
 
+// Drift of the centres since the last bounds call (v.prevc): drift[j] >=
+// ||c_j - c_j,prev|| (fp64, then 2^-40 and the fp32 round-up cover its
+// rounding), the largest, the second largest and the index of the largest
+// (a row whose own centre drifted most lowers its bound on the others by
+// the second largest).  A drift that is not finite sets drift_bad: every
+// row is then active.  One block; k <= W32_HINT_KMAX <= 256 threads' worth.
+__global__ void __launch_bounds__(256) k_drift(const double *__restrict__ C,
+                                               int64_t k, int64_t d,
+                                               WsView v) {
+  __shared__ float sd[256];
+  const int j = threadIdx.x;
+  float dj = 0.f;
+  if (j < k) {
+    double a = 0.0;
+    for (int64_t t = 0; t < d; ++t) {
+      const double df = C[j * d + t] - v.prevc[j * d + t];
+      a = fma(df, df, a);
+    }
+    dj = __double2float_ru(sqrt(a) * (1.0 + 0x1.0p-40));
+    v.drift[j] = dj;
+  }
+  sd[j] = dj;
+  __syncthreads();
+  if (j == 0) {
+    float m1 = 0.f, m2 = 0.f;
+    int im = 0;
+    bool bad = false;
+    for (int c = 0; c < (int)k; ++c) {
+      const float x = sd[c];
+      if (!(x < INFINITY)) bad = true;  // inf or NaN
+      if (x > m1) {
+        m2 = m1;
+        m1 = x;
+        im = c;
+      } else if (x > m2) {
+        m2 = x;
+      }
+    }
+    v.hdr->dmax1 = m1;
+    v.hdr->dmax2 = m2;
+    v.hdr->dimax = im;
+    v.hdr->drift_bad = bad ? 1u : 0u;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // update: C[c] = sums/counts (counts != 0), per-centre shift, criterion
 // ---------------------------------------------------------------------------
@@ -611,6 +668,7 @@ int dkm_prepare_centers(const double *C, int64_t k, int64_t d, int flags,
                                                             4096));
     k_frag<<<(unsigned)g, 256, 0, s>>>(C, k, d, v);
     if (v.mind) k_mind<<<(unsigned)k, 256, 0, s>>>(C, k, d, v.mind);
+    if (v.prevc) k_drift<<<1, 256, 0, s>>>(C, k, d, v);
   }
   if (int r = check_launch("dkm_prepare_centers")) return r;
   if (gemm_path(k, d) && !(flags & DKM_PREP_CSR))
@@ -678,6 +736,25 @@ int dkm_screen_counters(const void *ws, int64_t *out, void *stream) {
   out[3] = (int64_t)h.sfall_total;
   return 0;
 }
+
+int dkm_bounds_counters(const void *ws, int64_t *out, void *stream) {
+  if (!ws || !out) return fail(DKM_E_ARG, "bounds_counters: NULL");
+  WsHeader h;
+  hipError_t e = hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost,
+                                (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail((int)e, std::string("bounds_counters: ") +
+                            hipGetErrorString(e));
+  if (h.magic != WS_MAGIC) return fail(DKM_E_ARG, "bounds_counters: bad ws");
+  out[0] = (int64_t)h.bnd_calls;
+  out[1] = (int64_t)h.bnd_active;
+  out[2] = (int64_t)h.bnd_skipped;
+  out[3] = (int64_t)h.bnd_list_calls;
+  return 0;
+}
+
+int dkm_bounds_ok(int64_t k, int64_t d) { return bounds_shape(k, d) ? 1 : 0; }
 
 int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
                      void *stream) {

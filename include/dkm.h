@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 3
+#define DKM_ABI_VERSION 4
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -102,7 +102,9 @@ size_t dkm_workspace_bytes(int64_t k, int64_t d, int64_t n_queue);
  * order, error-bound scalars, optionally C^T) into the workspace and ZERO the
  * accumulator acc[k*(d+1)] ([sums | counts]) when acc != NULL.  Replaces the
  * implicit per-task centre broadcast of base.py:110,114 (and sklearn's
- * row_norms of the centres, recomputed per sample by the reference).      */
+ * row_norms of the centres, recomputed per sample by the reference).
+ * For dkm_bounds_ok(k, d) shapes it also computes every centre's drift
+ * since the last dkm_assign_delta_bounds_* call on this workspace.        */
 int dkm_prepare_centers(const double *C, int64_t k, int64_t d, int flags,
                         void *ws, size_t ws_bytes, double *acc, void *stream);
 
@@ -234,6 +236,54 @@ int dkm_assign_delta_img_f32(const float *X, const void *image, int image_kind,
                              int64_t ldx, const double *C, int64_t k,
                              const void *ws, size_t ws_bytes, int32_t *labels,
                              double *delta, int mode, void *stream);
+
+/* dkm_assign_delta_img_* with per-row distance bounds (Hamerly's pair) kept
+ * by the caller between the calls of one Lloyd loop: ub[i] >= the distance
+ * of row i to its label's centre, lb[i] <= its distance to every other
+ * centre (fp32[n] each, 16-B aligned like labels; rank-local).  A row with
+ * ub < lb provably keeps its label and is neither read nor scored; every
+ * other row goes through the screen and the exact re-check as in
+ * dkm_assign_delta_img_*, so labels and delta are identical to that call's.
+ *   bounds_flags = DKM_BOUNDS_INIT: ub / lb hold nothing yet (first call, or
+ *     the labels were written by any other call since the last one): every
+ *     row is screened from the image and gets its bounds.
+ *   bounds_flags = 0: the previous call on (ws, labels, ub, lb) was a bounds
+ *     call.  The drift of every centre since that call is computed by
+ *     dkm_prepare_centers from the centres the workspace kept (never taken
+ *     from the caller: any centre set is covered; a drift that is not
+ *     finite makes every row active), the bounds pass moves ub / lb by it
+ *     and lists the rows with !(ub < lb), and the list is screened from X.
+ *     When more than 45 % of the rows are active (the measured crossover;
+ *     DKM_BOUNDS_LIST_FRAC in the environment overrides it), the image
+ *     screen over all rows runs instead; the choice is made on the device.
+ *     DKM_BOUNDS_INIT calls run no bounds pass and are not counted by
+ *     dkm_bounds_counters.
+ * Shapes: dkm_bounds_ok(k, d) (d <= 32, 2 <= k <= 256; any ldx), mode
+ * AUTO or SCREEN_BF16X3 without flags, a built DKM_IMAGE_SPLIT image, a
+ * workspace with n label slots (dkm_workspace_bytes(k, d, n_queue >= n));
+ * anything else is refused with DKM_E_ARG.  Replaces the same reference
+ * code as dkm_assign_delta_* (base.py:166-181).
+ * dkm_bounds_counters (host, syncs `stream`): over the workspace's life,
+ * out[0] calls that ran the bounds pass, out[1] rows it left active, out[2]
+ * rows it skipped, out[3] calls whose active rows were screened as a list
+ * (out has 4 entries).                                                     */
+#define DKM_BOUNDS_INIT 1
+int dkm_bounds_ok(int64_t k, int64_t d);
+int dkm_assign_delta_bounds_f64(const double *X, const void *image,
+                                int image_kind, size_t image_bytes, int64_t n,
+                                int64_t d, int64_t ldx, const double *C,
+                                int64_t k, const void *ws, size_t ws_bytes,
+                                int32_t *labels, double *delta, int mode,
+                                float *ub, float *lb, int bounds_flags,
+                                void *stream);
+int dkm_assign_delta_bounds_f32(const float *X, const void *image,
+                                int image_kind, size_t image_bytes, int64_t n,
+                                int64_t d, int64_t ldx, const double *C,
+                                int64_t k, const void *ws, size_t ws_bytes,
+                                int32_t *labels, double *delta, int mode,
+                                float *ub, float *lb, int bounds_flags,
+                                void *stream);
+int dkm_bounds_counters(const void *ws, int64_t *out, void *stream);
 
 /* acc[k*(d+1)] += [sums | counts] of the rows of X by labels (label < 0 or
  * >= k: skipped): the sums half of dkm_partial_sum for known labels.       */
