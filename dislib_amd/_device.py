@@ -403,7 +403,7 @@ def sorted_image_ok(dd, k):
     if dd.sparse or dd.n == 0 or not X_IMAGE:
         return False
     # the screen that maintains the image reads 16-B pieces of X's rows
-    # (dkm_dense.hip launch_screen `vec`): rows a multiple of 16 B apart,
+    # (dkm_dense.hip plan_screen `vec`): rows a multiple of 16 B apart,
     # X 16-B aligned (d % 8 == 0 is checked by dkm_x_image_sorted_ok)
     isz = dd.X.element_size()
     if (dd.X.stride(0) * isz) % 16 or dd.X.data_ptr() % 16:

@@ -17,10 +17,8 @@
 //                      split precision), a rigorous error bound decides
 //                      whether the screened winner IS the reference winner;
 //                      otherwise the label is left for the re-check.
-//   k_recheck_lane     undecided samples, compacted per wave, lane per
-//                      sample: fp32 re-screen, then the reference
-//                      arithmetic on the remaining candidate centres.
-//   k_recheck_exact    the reference arithmetic on all centres (any d, k).
+//   (dkm_recheck.hip)  k_recheck_*: the undecided samples, by an fp32
+//                      re-screen and the reference arithmetic.
 //
 // Toolchain note (ROCm 7.2, gfx950): no packed-fp32 VALU (v_pk_fma_f32 and
 // friends) in these kernels.  hipcc reused a source VGPR of a v_pk_fma_f32
@@ -29,15 +27,7 @@
 // at random (tools/debug_mismatch.py pinned it to MFMA row 13 = lanes 48-63,
 // element 1).  Scalar fmaf + -fno-slp-vectorize; tests check the ISA.
 //
-// Accumulation (acc = [sums k*d | counts k], fp64):
-//   full   every sample adds its row (partial_sum semantics);
-//   delta  incremental: labels[] holds the previous assignment; only samples
-//          whose label changes add +x to the new and -x to the old cluster
-//          (dkm_assign_delta).
-// Both go to block-private LDS accumulators (odd row stride, flushed once
-// per block) when they fit, else to fp64 global atomics.  Delta in LDS
-// matters: in the first iterations most labels move, and global atomics on
-// k rows serialise (a 100M x 32, k = 100 delta pass took 650 ms that way).
+// (Accumulation modes and the LDS accumulators: dkm_dense.h.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,31 +36,12 @@
 #include <cstdlib>
 #include <string>
 
-#include "dkm_internal.h"
+#include "dkm_dense.h"
 
 namespace dkm {
 
-constexpr int BLOCK = 256;
-constexpr size_t LDS_BUDGET = 80 * 1024;  // per block -> >= 2 blocks / CU
-constexpr size_t LDS_PER_CU = 160 * 1024;
-
-// Accumulation mode bits: AM_ON (accumulate at all), AM_DELTA (incremental:
-// only label changes move rows), AM_INLDS (block-private LDS accumulators,
-// flushed once per block; else fp64 global atomics).
-// AM_MLIST (k_screen_w32, with AM_DELTA and without AM_ON): the rows the
-// screen moves are listed (v.smoved, count hdr->nmoved; previous labels in
-// v.queue[row]) for sorted_sums_moved instead of added in the screen.
-enum : int { AM_NONE = 0, AM_ON = 1, AM_DELTA = 2, AM_INLDS = 4,
-             AM_MLIST = 8 };
 constexpr int W32_MLB = 256;  // AM_MLIST: moved rows staged per wave (LDS)
-__host__ __device__ __forceinline__ bool am_full(int m) {
-  return (m & (AM_ON | AM_DELTA)) == AM_ON;
-}
-
-struct DevInfo {
-  int cus = 256;
-};
-static DevInfo dev_info() {
+DevInfo dev_info() {
   static thread_local int cached_dev = -1;
   static thread_local DevInfo info;
   int dev = 0;
@@ -93,7 +64,7 @@ static DevInfo dev_info() {
 // waves per SIMD), so it is not used.  A/B builds (variants.sh) may pin the
 // count with -DDKM_AB_BLOCKS_PER_CU=n and print the numbers with
 // -DDKM_AB_VERBOSE; the product build has neither.
-static int resident_blocks(const void *kf, int block, size_t lds) {
+int resident_blocks(const void *kf, int block, size_t lds) {
 #ifdef DKM_AB_BLOCKS_PER_CU
   return DKM_AB_BLOCKS_PER_CU;
 #endif
@@ -120,57 +91,6 @@ static int resident_blocks(const void *kf, int block, size_t lds) {
   return own;
 }
 
-template <class TX>
-__device__ __forceinline__ double ld_x(const TX *p) {
-  return (double)(*p);
-}
-
-// LDS accumulators: row stride of an odd number of doubles, so that the
-// rows of different clusters start in different banks (a 32-double row is
-// exactly one 256-B bank row: unpadded, every cluster's feature t sits in
-// the same bank and same-feature adds of different clusters serialise).
-__host__ __device__ __forceinline__ int lds_stride(int d) {
-  return (d & 1) ? d : d + 1;
-}
-__host__ __device__ __forceinline__ int64_t lds_acc_len(int64_t k, int d) {
-  return k * lds_stride(d) + k;
-}
-
-__device__ __forceinline__ void lds_add(double *p, double v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Where one kernel's sums go: LDS rows (odd stride) or the global acc.
-struct AccTarget {
-  double *rows;
-  double *cnt;
-  int stride;
-  bool lds;
-  __device__ __forceinline__ void add(int row, int t, double v) const {
-    double *p = rows + (int64_t)row * stride + t;
-    if (lds)
-      lds_add(p, v);
-    else
-      atomic_add_f64(p, v);
-  }
-  __device__ __forceinline__ void count(int row, double v) const {
-    if (lds)
-      lds_add(cnt + row, v);
-    else
-      atomic_add_f64(cnt + row, v);
-  }
-};
-
-__device__ __forceinline__ AccTarget acc_target(int amode, double *lds_acc,
-                                                double *acc, int64_t k,
-                                                int d) {
-  if (amode & AM_INLDS) {
-    const int ds = lds_stride(d);
-    return AccTarget{lds_acc, lds_acc + k * ds, ds, true};
-  }
-  return AccTarget{acc, acc + k * d, d, false};
-}
-
 // Accumulate one sample (lane-per-sample kernels): +x to `label`, and in
 // delta mode (only when the label changed) -x from `prev`.
 template <class TX>
@@ -188,23 +108,6 @@ __device__ __forceinline__ void acc_row_lane(int amode, const AccTarget &a,
   }
   a.count(label, 1.0);
   if (sub) a.count(prev, -1.0);
-}
-
-__device__ __forceinline__ void zero_lds_acc(double *lds_acc, int64_t k,
-                                             int d) {
-  const int64_t len = lds_acc_len(k, d);
-  for (int64_t e = threadIdx.x; e < len; e += blockDim.x) lds_acc[e] = 0.0;
-}
-
-__device__ __forceinline__ void flush_lds_acc(const double *lds_acc,
-                                              double *acc, int64_t k, int d) {
-  const int ds = lds_stride(d);
-  const int64_t kd = k * d;
-  for (int64_t e = threadIdx.x; e < kd + k; e += blockDim.x) {
-    const double v = e < kd ? lds_acc[(e / d) * ds + (e % d)]
-                            : lds_acc[k * ds + (e - kd)];
-    if (v != 0.0) atomic_add_f64(acc + e, v);
-  }
 }
 
 // ---------------------------------------------------------------------------
@@ -352,219 +255,20 @@ __global__ void __launch_bounds__(BLOCK)
 namespace dkm {
 
 
-#ifndef DKM_SB
-#define DKM_SB 512
-#endif
-// NB1: 16-sample blocks per wave step at d <= 32.  WPE: waves per SIMD the
-// d <= 32 screen is compiled for (6 -> <= 80 VGPRs -> three 512-thread
-// blocks per CU; NB1 = 2 needs ~150 VGPRs, one block per CU); d <= 64: 4.
-#ifndef DKM_NB1
-#define DKM_NB1 1
-#endif
-#ifndef DKM_WPE
-#define DKM_WPE 6
-#endif
+// SB: the screen block (SB/64 waves share one LDS image).  NB1: 16-sample
+// blocks per wave step at d <= 32.  Waves per SIMD the screen is compiled
+// for: d <= 32, 6 (<= 80 VGPRs -> three 512-thread blocks per CU; NB1 = 2
+// needs ~150 VGPRs, one block per CU); d <= 64, 4.
 // CHUNK (fragments staged through LDS): one 512-thread block per CU (the
 // chunk fills the LDS), so 2 waves per SIMD whatever the registers: compiled
 // for 2 waves per EU (up to 256 VGPRs) instead of d <= 64's 4 -- C3
 // iteration 0's bf16x3 screen 60-61 -> 54 ms (r05nb kernel traces).  Two
 // 16-sample blocks per wave step (half the L2 -> LDS fragment traffic per
 // row) measured slower, 68.5 ms: NB_CHUNK stays 1.
-#ifndef DKM_NB_CHUNK
-#define DKM_NB_CHUNK 1
-#endif
+constexpr int SB = 512, NB1 = 1, NB_CHUNK = 1;
 #define DKM_SCREEN_WPE(NKS, CHUNK) \
   __attribute__((amdgpu_waves_per_eu( \
-      (CHUNK) ? 2 : DKM_WPE <= 0 ? 1 : (NKS) == 1 ? DKM_WPE : (NKS) == 2 ? 4 : 1)))
-constexpr int SB = DKM_SB;  // screen block: SB/64 waves share one LDS image
-
-// A/B switches, compile-time only (variants.sh -DDKM_AB_...=1; all off in the
-// product build): no W32 screen, delta sums always / never by k_label_sums,
-// no per-wave undecided lists, post-screen sums by k_label_sums instead of
-// the sorted sums.
-#ifndef DKM_AB_LABEL_SUMS
-#define DKM_AB_LABEL_SUMS 0
-#endif
-#ifndef DKM_AB_NO_W32
-#define DKM_AB_NO_W32 0
-#endif
-#ifndef DKM_AB_NO_C32
-#define DKM_AB_NO_C32 0
-#endif
-constexpr bool AB_NO_C32 = DKM_AB_NO_C32;
-#ifndef DKM_AB_NO_GEMM_BUILD
-#define DKM_AB_NO_GEMM_BUILD 0
-#endif
-constexpr bool AB_NO_GEMM_BUILD = DKM_AB_NO_GEMM_BUILD;
-#ifndef DKM_AB_NO_MLIST
-#define DKM_AB_NO_MLIST 0
-#endif
-constexpr bool AB_NO_MLIST = DKM_AB_NO_MLIST;
-#ifndef DKM_AB_DELTA_POST
-#define DKM_AB_DELTA_POST 0
-#endif
-#ifndef DKM_AB_NO_POST
-#define DKM_AB_NO_POST 0
-#endif
-#ifndef DKM_AB_NO_LIST
-#define DKM_AB_NO_LIST 0
-#endif
-constexpr bool AB_NO_W32 = DKM_AB_NO_W32, AB_DELTA_POST = DKM_AB_DELTA_POST,
-               AB_NO_POST = DKM_AB_NO_POST, AB_NO_LIST = DKM_AB_NO_LIST,
-               AB_LABEL_SUMS = DKM_AB_LABEL_SUMS;
-
-// Eight consecutive features t0..t0+7 of one row, as fp64.  VEC: d % 8 == 0
-// and 16-B aligned rows, so the 8 features are in range iff t0 < d.
-template <bool VEC, class TX>
-__device__ __forceinline__ void load8(const TX *xr, int t0, int d,
-                                      double (&o)[8]) {
-  if (VEC) {
-    if (t0 < d) {
-      if constexpr (sizeof(TX) == 8) {
-        const double2 *p = (const double2 *)(xr + t0);
-        const double2 a = p[0], b = p[1], c = p[2], e = p[3];
-        o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-        o[4] = c.x; o[5] = c.y; o[6] = e.x; o[7] = e.y;
-      } else {
-        const float4 *p = (const float4 *)(xr + t0);
-        const float4 a = p[0], b = p[1];
-        o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-        o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-      }
-    } else {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) o[m] = 0.0;
-    }
-  } else {
-#pragma unroll
-    for (int m = 0; m < 8; ++m)
-      o[m] = (t0 + m < d) ? (double)xr[t0 + m] : 0.0;
-  }
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// One undecided sample per lane (the screen's tail and k_recheck_lane).
-// Stage 1 re-screens in fp32 VALU (x in VGPRs, fp32 centres `cl` of row
-// stride dp and |c|^2 `cnl`, in LDS or global memory) -- the P_F32
-// arithmetic and bound, ~2^-24 instead of bf16x3's ~2^-16 -- and keeps the
-// label when the best two scores are 2B apart.  Otherwise stage 2 runs the
-// reference arithmetic on the candidates only (score <= best + 2B: the
-// reference winner is always among them, and every other centre is
-// strictly farther after sqrt).  Writes lab_out[i] and moves
-// the row between the accumulators as amode says (prev = previous label).
-// STAGE1_ONLY: return false (writing nothing) when stage 1 cannot decide,
-// so the caller can batch the rare stage-2 samples into full waves.
-template <int MAXD, bool VEC, class TX, bool STAGE1_ONLY = false>
-__device__ __forceinline__ bool resolve_lane(
-    const TX *__restrict__ X, int64_t ldx, int d, int k, int64_t i, int prev,
-    const float *cl, const float *cnl, int dp, float cm, const double *ct64,
-    int32_t *lab_out, int amode, const AccTarget &at) {
-  const TX *xr = X + i * ldx;
-  float xf[MAXD];
-  float xx = 0.f;
-#pragma unroll
-  for (int b = 0; b < MAXD / 8; ++b) {
-    double o[8];
-    if (8 * b < d) {
-      load8<VEC>(xr, 8 * b, d, o);
-    } else {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) o[m] = 0.0;
-    }
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      xf[8 * b + m] = (float)o[m];
-      xx = fmaf(xf[8 * b + m], xf[8 * b + m], xx);
-    }
-  }
-  // fp32 score of centre jc: fma chain over features (padding adds 0 * 0).
-  // cl / cnl are the workspace's global fp32 centres, read through the
-  // constant address space: jc is wave-uniform, so the rows arrive by scalar
-  // loads into SGPRs (an LDS broadcast of the same row costs the full LDS
-  // return bandwidth, twice the VALU time of the fma chain).
-  typedef const __attribute__((address_space(4))) float cfloat;
-  typedef const __attribute__((address_space(4))) f32x4 cf32x4;
-  cfloat *clc = (cfloat *)cl;
-  cfloat *cnc = (cfloat *)cnl;
-  // full rows (dp == MAXD): no per-chunk branch, so the row's scalar loads
-  // issue together (one wait instead of one per 4 features)
-  const bool full = dp == MAXD;
-  auto score = [&](int jc) {
-    cfloat *cr = clc + (int64_t)jc * dp;
-    float dot = 0.f;
-    if (full) {
-#pragma unroll
-      for (int t4 = 0; t4 < MAXD / 4; ++t4) {
-        const f32x4 c4 = *(cf32x4 *)(cr + 4 * t4);
-        dot = fmaf(xf[4 * t4 + 0], c4.x, dot);
-        dot = fmaf(xf[4 * t4 + 1], c4.y, dot);
-        dot = fmaf(xf[4 * t4 + 2], c4.z, dot);
-        dot = fmaf(xf[4 * t4 + 3], c4.w, dot);
-      }
-    } else {
-#pragma unroll
-      for (int t4 = 0; t4 < MAXD / 4; ++t4) {
-        if (4 * t4 < dp) {
-          const f32x4 c4 = *(cf32x4 *)(cr + 4 * t4);
-          dot = fmaf(xf[4 * t4 + 0], c4.x, dot);
-          dot = fmaf(xf[4 * t4 + 1], c4.y, dot);
-          dot = fmaf(xf[4 * t4 + 2], c4.z, dot);
-          dot = fmaf(xf[4 * t4 + 3], c4.w, dot);
-        }
-      }
-    }
-    return fmaf(-2.f, dot, cnc[jc]);
-  };
-  float b1 = INFINITY, b2 = INFINITY;
-  int i1 = 0;
-#ifndef DKM_S1_UNROLL
-#define DKM_S1_UNROLL 4
-#endif
-#pragma unroll DKM_S1_UNROLL
-  for (int jc = 0; jc < k; ++jc) {
-    const float sc = score(jc);
-    i1 = sc < b1 ? jc : i1;
-    b2 = __builtin_amdgcn_fmed3f(b1, b2, sc);
-    b1 = fminf(b1, sc);
-  }
-  const float xn = sqrtf(xx) * (1.0f + (d + 4) * 0x1.0p-24f);
-  const float B = screen_bound<P_F32>(d, xn, cm, false);
-  const bool sane = (xn < 1e18f) && (xn * cm < 1e30f) && (b1 < 1e30f);
-  int bi = i1;
-  if (!(sane && b2 - b1 > 2.0f * B)) {
-    if constexpr (STAGE1_ONLY) return false;
-    const float lim = b1 + 2.0f * B;
-    double best = INFINITY;
-    bi = -1;
-#pragma unroll 1
-    for (int jc = 0; jc < k; ++jc) {
-      if (sane && !(score(jc) <= lim)) continue;
-      const SqDiffT<TX> f{xr, ct64 + jc, ct_ld(k)};
-      const double dist = argmin_key(sqrt(pw_leaf(f, 0, d)));
-      if (dist < best || bi < 0) {
-        best = dist;
-        bi = jc;
-      }
-    }
-  }
-  lab_out[i] = bi;
-  if (!(amode & AM_ON)) return true;
-  const bool delta = amode & AM_DELTA;
-  if (delta && bi == prev) return true;
-  const bool sub = delta && prev >= 0;
-  for (int t = 0; t < d; ++t) {
-    const double x = ld_x(xr + t);
-    at.add(bi, t, x);
-    if (sub) at.add(prev, t, -x);
-  }
-  at.count(bi, 1.0);
-  if (sub) at.count(prev, -1.0);
-  return true;
-}
+      (CHUNK) ? 2 : (NKS) == 1 ? 6 : (NKS) == 2 ? 4 : 1)))
 
 // One wave = NB blocks of 16 samples per step.  Lane l = (q = l >> 4,
 // j = l & 15) holds features ks*32 + 8q + m (m < 8) of sample j of every
@@ -776,9 +480,7 @@ __global__ void __launch_bounds__(SB) DKM_SCREEN_WPE(NKS, CHUNK)
     for (int b = 0; b < NB; ++b) prv[b] = pv[b];
     // ---- the next step's rows stream in while this one computes ----
     const int64_t s_next = s0 + step;
-#ifndef DKM_DBG_NOLOAD
     if (!full_acc && s_next < n) load_tile(s_next);
-#endif
 
     // running (value, centre index) top-2 of this lane over all groups
     // (T3: top-3, the second's index in ri2)
@@ -830,12 +532,6 @@ __global__ void __launch_bounds__(SB) DKM_SCREEN_WPE(NKS, CHUNK)
         }
       }
     };
-#ifdef DKM_DBG_NOCOMPUTE
-    for (int b = 0; b < NB; ++b) {
-      r1[b] = xx[b];
-      r2[b] = 1e20f;
-    }
-#else
     for (int c0 = 0; c0 < nkb; c0 += lkb) {
     const int c1 = min(nkb, c0 + lkb);
     if (CHUNK) {
@@ -914,7 +610,6 @@ __global__ void __launch_bounds__(SB) DKM_SCREEN_WPE(NKS, CHUNK)
       }
     }
     }  // chunks
-#endif
     // merge the top-2 of the four lanes of a sample
     // (symmetric in the pair: both lanes get the same result whichever
     // order pair_xor hands the two sides over)
@@ -1075,13 +770,6 @@ __device__ __forceinline__ void wave_sync_w() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-// cache policy of k_screen_w32's streaming row loads (0 = default; 2 = NT)
-#ifndef DKM_XLOAD_AUX
-#define DKM_XLOAD_AUX 0
-#endif
-#ifndef DKM_W32_WPE
-#define DKM_W32_WPE 3
-#endif
 // HINT (image delta launches, k <= W32_HINT_KMAX: the steady iterations of
 // C2): a threshold pass, as k_screen_b2's.  With p = the row's incoming
 // label, s_hat_p comes from v_dot2 products of the same bf16x3 operands
@@ -1122,7 +810,7 @@ struct BndArgs {
 };
 template <class TX, bool IMG, bool HINT = false, bool BND = false>
 __global__ void __launch_bounds__(SBW) __attribute__((
-    amdgpu_waves_per_eu(DKM_W32_WPE)))
+    amdgpu_waves_per_eu(3)))
     k_screen_w32(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
                  int k, WsView v, int32_t *__restrict__ lab_out, double *acc,
                  int amode, int64_t base, int use_list, XImage img,
@@ -1287,8 +975,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
         }
         raw[c][i] = __builtin_bit_cast(
             txv, __builtin_amdgcn_raw_buffer_load_b128(
-                     rx, lane_off[i] + 16 * c * (int)sizeof(TX), 0,
-                     DKM_XLOAD_AUX));
+                     rx, lane_off[i] + 16 * c * (int)sizeof(TX), 0, 0));
       }
   };
   auto tx_addr = [](int row, int q) {  // 16-B quarter q of a 32-B row
@@ -1944,10 +1631,7 @@ static int launch_screen_c32(const TX *X, int64_t end, int d, int64_t ldx,
 // register prefetch of the next tile -- the CU's other waves cover a
 // wave's load (at 2 waves per SIMD with a prefetched tile the kernel waited
 // 48% of its cycles: PMC r02a)
-#ifndef DKM_AB_SBB
-#define DKM_AB_SBB 768
-#endif
-constexpr int SBB = DKM_AB_SBB;
+constexpr int SBB = 768;
 constexpr uint32_t PACK1 = 9, PACK1_MASK = (1u << PACK1) - 1;
 // threshold pass: at most this many of a wave's 32 samples may end with an
 // over-full (or unusable) candidate list before the wave redoes the tile
@@ -2059,15 +1743,8 @@ __global__ void __launch_bounds__(SBB)
   };
 
   typedef float f32x16 __attribute__((ext_vector_type(16)));
-#ifndef DKM_AB_B1_PREFETCH
-#define DKM_AB_B1_PREFETCH 0
-#endif
-  // A/B: prefetch the next tile (and its labels) into the tile registers
-  // as soon as the current one is converted (needs ~64 more VGPRs: pair
-  // with a smaller block, -DDKM_AB_SBB=512)
-  if (DKM_AB_B1_PREFETCH && base + wv * 32 < n) load_tile(base + wv * 32);
   for (int64_t s0 = base + wv * 32; s0 < n; s0 += step) {
-    if (!DKM_AB_B1_PREFETCH) load_tile(s0);
+    load_tile(s0);
     float xx = 0.f;
     bf16x8 xh[NKS];
 #pragma unroll
@@ -2088,7 +1765,6 @@ __global__ void __launch_bounds__(SBB)
       xx = xa + xb;
     }
     const int prv = pv;
-    if (DKM_AB_B1_PREFETCH && s0 + step < n) load_tile(s0 + step);
     const int64_t si = s0 + r;
     float xn;
     const float B2 = bound2_fast(bk, xx, xn);
@@ -2162,16 +1838,7 @@ __global__ void __launch_bounds__(SBB)
         // own centre poisoned means an ambiguous sample (rare).  Per-group
         // branches (16 VALU, 4 branches a block) ran 28.3 against 26.6 ms
         // per C3 step (profiles/r02/ab_m3/).
-#ifndef DKM_AB_B1_PROBE
-#define DKM_AB_B1_PROBE 0
-#endif
-        float probe = 0.f;  // A/B timing probes only (results invalid)
         auto test_blk = [&](const f32x16 &accv, float (&m)[8], bool &any) {
-          if (DKM_AB_B1_PROBE == 2) {
-            probe = fmaxf(probe, accv[0]);
-            any = false;
-            return;
-          }
 #pragma unroll
           for (int i = 0; i < 8; ++i)
             m[i] = __builtin_amdgcn_fmed3f(accv[2 * i], accv[2 * i + 1], ninf);
@@ -2181,10 +1848,6 @@ __global__ void __launch_bounds__(SBB)
           any = fminf(b, c) <= T;
         };
         auto append = [&](int cb, const f32x16 &accv, const bool (&gh)[4]) {
-          if (DKM_AB_B1_PROBE) {
-            probe += (gh[0] | gh[1] | gh[2] | gh[3]) ? 1.f : 0.f;
-            return;
-          }
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             if (gh[q]) {
@@ -2279,11 +1942,6 @@ __global__ void __launch_bounds__(SBB)
             test_blk(acc_a, ma, ga);
             append_blk(cb, acc_a, ma, ga);
           }
-        }
-        if (DKM_AB_B1_PROBE) {  // keep the hint as the only candidate
-          cnt = (probe == 12345.f || h != ((pw >> 2) & 1)) ? 0 : 1;
-          q0 = sp;
-          j0 = p;
         }
         // the sample's two lanes: union of their kept lists
         int ocnt, oj0, oj1, oj2;
@@ -2571,403 +2229,6 @@ __global__ void __launch_bounds__(BLOCK)
   if (mine) atomicAdd((unsigned long long *)&v.hdr->rechecked_total, mine);
 }
 
-// Exact re-check of the samples the screen left undecided (lab_out < 0,
-// encoding the previous label as -(prev + 2)).  Waves scan 64 labels at a
-// time (coalesced, no shared counter).
-//   k_recheck_lane (d <= 128, fp32 centres fit in LDS): each wave compacts
-//     its undecided samples into an LDS list and resolves them 64 at a time,
-//     lane = sample.  Stage 1 re-screens in fp32 VALU (x in VGPRs, centres
-//     broadcast from LDS) -- the P_F32 arithmetic and bound, ~2^-24 instead
-//     of bf16x3's ~2^-16 -- and keeps the label when the best two scores are
-//     2B apart.  Otherwise stage 2 runs the reference arithmetic on the
-//     candidates only (score <= best + 2B: the reference winner is always
-//     among them, and every other centre is strictly farther after sqrt,
-//     DESIGN.md 3.1).
-//   k_recheck_exact (any d, k): wave per sample, lanes over centres, the
-//     reference arithmetic on every centre.
-template <class TX>
-__device__ __forceinline__ void recheck_accumulate(int amode,
-                                                   const AccTarget &at,
-                                                   const TX *xr, int d,
-                                                   int bi, int prev,
-                                                   int lane) {
-  if (!(amode & AM_ON)) return;
-  const bool delta = amode & AM_DELTA;
-  if (delta && bi == prev) return;
-  const bool sub = delta && prev >= 0;
-  for (int t = lane; t < d; t += 64) {
-    const double x = ld_x(xr + t);
-    at.add(bi, t, x);
-    if (sub) at.add(prev, t, -x);
-  }
-  if (lane == 0) {
-    at.count(bi, 1.0);
-    if (sub) at.count(prev, -1.0);
-  }
-}
-
-__device__ __forceinline__ void recheck_finish_count(
-    unsigned long long mine, unsigned long long *blk_count, const WsView &v) {
-  if ((threadIdx.x & 63) == 0 && mine)
-    __hip_atomic_fetch_add(blk_count, mine, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_WORKGROUP);
-  __syncthreads();
-  if (threadIdx.x == 0 && *blk_count)
-    atomicAdd((unsigned long long *)&v.hdr->rechecked_total, *blk_count);
-}
-
-// resolve_lane's two stages for ONE sample i with the whole wave: lanes
-// over centres (jc = lane, lane + 64, ...), the same fp32 scores and bound
-// (stage 1), then the reference arithmetic on the centres within the bound
-// (stage 2; every centre when the scores are not sane), reduced over the
-// wave by (distance, index).  The re-check list's stage-2 samples go here:
-// lane per sample, a sample with many candidates (a near-tie among many
-// centres) held its whole wave for k sequential exact distances.
-template <int MAXD, class TX>
-__device__ __forceinline__ void resolve_wave(
-    const TX *__restrict__ X, int64_t ldx, int d, int k, int64_t i, int prev,
-    const float *cl, const float *cnl, int dp, float cm, const double *ct64,
-    int32_t *lab_out, int amode, const AccTarget &at) {
-  const int lane = threadIdx.x & 63;
-  const TX *xr = X + i * ldx;
-  float xf[MAXD];
-  float xx = 0.f;
-#pragma unroll
-  for (int t = 0; t < MAXD; ++t) {      // the same fp32 chain as resolve_lane
-    xf[t] = t < d ? (float)ld_x(xr + t) : 0.f;
-    xx = fmaf(xf[t], xf[t], xx);
-  }
-  // the centre's fp32 row (dp floats, 16-B aligned) by 16-B loads, all
-  // issued before the fma chain (the same chain order as resolve_lane)
-  auto score = [&](int jc) {
-    const f32x4 *cr = (const f32x4 *)(cl + (int64_t)jc * dp);
-    f32x4 c4[MAXD / 4];
-#pragma unroll
-    for (int t4 = 0; t4 < MAXD / 4; ++t4)
-      if (4 * t4 < dp) c4[t4] = cr[t4];
-    float dot = 0.f;
-#pragma unroll
-    for (int t4 = 0; t4 < MAXD / 4; ++t4)
-      if (4 * t4 < dp) {
-        dot = fmaf(xf[4 * t4 + 0], c4[t4].x, dot);
-        dot = fmaf(xf[4 * t4 + 1], c4[t4].y, dot);
-        dot = fmaf(xf[4 * t4 + 2], c4[t4].z, dot);
-        dot = fmaf(xf[4 * t4 + 3], c4[t4].w, dot);
-      }
-    return fmaf(-2.f, dot, cnl[jc]);
-  };
-  float b1 = INFINITY, b2 = INFINITY;
-  int i1 = INT32_MAX;
-#pragma unroll 2
-  for (int jc = lane; jc < k; jc += 64) {
-    const float sc = score(jc);
-    i1 = sc < b1 ? jc : i1;
-    b2 = __builtin_amdgcn_fmed3f(b1, b2, sc);
-    b1 = fminf(b1, sc);
-  }
-  // wave top-2 (NaN scores never win: fminf / med3 drop them, and the sane
-  // test below sends such a sample to stage 2 over every centre)
-  for (int off = 1; off < 64; off <<= 1) {
-    const float o1 = __shfl_xor(b1, off, 64), o2 = __shfl_xor(b2, off, 64);
-    const int oi = __shfl_xor(i1, off, 64);
-    const bool tk = (o1 < b1) | ((o1 == b1) & (oi < i1));
-    b2 = tk ? fminf(b1, o2) : fminf(b2, o1);
-    i1 = tk ? oi : i1;
-    b1 = tk ? o1 : b1;
-  }
-  const float xn = sqrtf(xx) * (1.0f + (d + 4) * 0x1.0p-24f);
-  const float B = screen_bound<P_F32>(d, xn, cm, false);
-  const bool sane = (xn < 1e18f) && (xn * cm < 1e30f) && (b1 < 1e30f);
-  int bi = i1;
-  if (!(sane && b2 - b1 > 2.0f * B)) {
-    const float lim = b1 + 2.0f * B;
-    double best = INFINITY;
-    bi = INT32_MAX;
-    for (int jc = lane; jc < k; jc += 64) {
-      if (sane && !(score(jc) <= lim)) continue;
-      const SqDiffT<TX> f{xr, ct64 + jc, ct_ld(k)};
-      const double dist = argmin_key(sqrt(pw_leaf(f, 0, d)));
-      if (dist < best || bi == INT32_MAX) {
-        best = dist;
-        bi = jc;
-      }
-    }
-    for (int off = 1; off < 64; off <<= 1) {
-      const double ob = __shfl_xor(best, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      const bool tk = (ob < best) | ((ob == best) & (oi < bi));
-      best = tk ? ob : best;
-      bi = tk ? oi : bi;
-    }
-  }
-  if (lane == 0) lab_out[i] = bi;
-  recheck_accumulate(amode, at, xr, d, bi, prev, lane);
-}
-
-constexpr int RL_CAP = 128;  // per-wave list: a full batch + one chunk
-
-static size_t recheck_lane_lds(int64_t, int64_t) {
-  return (size_t)(BLOCK / 64) * RL_CAP * 8;
-}
-
-template <int MAXD, bool VEC, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_lane(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
-                   int k, WsView v, int32_t *__restrict__ lab_out,
-                   double *acc, int amode, int64_t base) {
-  if (v.hdr->qcount == 0) return;  // the screen resolved everything
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int dp = (int)round_up(d, 4);  // c32 row stride (dkm_util)
-  // (fp32 centres: global, scalar loads in resolve_lane)
-  int64_t *lists = (int64_t *)smem;
-  double *lds_acc = (double *)(lists + (BLOCK / 64) * RL_CAP);
-  __shared__ unsigned long long blk_count;
-  if (threadIdx.x == 0) blk_count = 0;
-  if (amode & AM_INLDS) zero_lds_acc(lds_acc, k, d);
-  const float cm =
-      (float)__longlong_as_double((long long)v.hdr->cmax_bits) * 1.000001f;
-  const AccTarget at = acc_target(amode, lds_acc, acc, k, d);
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  int64_t *wl = lists + (threadIdx.x >> 6) * RL_CAP;
-
-  auto resolve = [&](int64_t i) {
-    resolve_lane<MAXD, VEC, TX>(X, ldx, d, k, i, -lab_out[i] - 2, v.c32,
-                                v.cn32, dp,
-                                cm, v.ct64, lab_out, amode, at);
-  };
-
-  // Scan: 4 labels per lane (int4), 256 per wave step, the next step's
-  // labels in flight while this one resolves (a wave's list only holds
-  // samples of steps it has already scanned, so the prefetch is never stale).
-  // a0 aligns the int4 loads; lanes outside [base, n) read nothing.
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  const int64_t a0 =
-      base - (int64_t)(((uintptr_t)(lab_out + base) >> 2) & 3);
-  auto load4 = [&](int64_t c0, int (&o)[4]) {
-    const int64_t i0 = c0 + 4 * lane;
-    if (i0 >= base && i0 + 3 < n) {
-      const int4 q4 = *(const int4 *)(lab_out + i0);
-      o[0] = q4.x; o[1] = q4.y; o[2] = q4.z; o[3] = q4.w;
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        o[c] = (i0 + c >= base && i0 + c < n) ? lab_out[i0 + c] : 0;
-    }
-  };
-  unsigned long long mine = 0;
-  int cnt = 0;  // wave-uniform list length
-  int cur[4] = {0, 0, 0, 0};
-  int64_t c0 = a0 + wv * 256;
-  if (c0 < n) load4(c0, cur);
-  for (; c0 < n; c0 += nwv * 256) {
-    int nxt[4] = {0, 0, 0, 0};
-    if (c0 + nwv * 256 < n) load4(c0 + nwv * 256, nxt);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const unsigned long long mask = __ballot(cur[c] < 0);
-      if (cur[c] < 0)
-        wl[cnt + __popcll(mask & ((1ull << lane) - 1))] = c0 + 4 * lane + c;
-      const int add = __popcll(mask);
-      mine += add;
-      cnt += add;
-      if (cnt >= 64) {
-        wave_lds_sync();
-        resolve(wl[lane]);
-        const int rem = cnt - 64;
-        const int64_t tail = lane < rem ? wl[64 + lane] : 0;
-        wave_lds_sync();
-        if (lane < rem) wl[lane] = tail;
-        cnt = rem;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) cur[c] = nxt[c];
-  }
-  wave_lds_sync();
-  if (lane < cnt) resolve(wl[lane]);
-  recheck_finish_count(mine, &blk_count, v);
-  if (amode & AM_INLDS) flush_lds_acc(lds_acc, acc, k, d);
-}
-
-#ifndef DKM_LIST_SPREAD
-#define DKM_LIST_SPREAD 1
-#endif
-// The screen's per-wave lists (WsView::tlist/tcount, nseg segments): lane
-// per listed sample (resolve_lane), fp32 centres in LDS.  No label scan:
-// the work is proportional to the undecided samples only.
-template <int MAXD, bool VEC, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_list(const TX *__restrict__ X, int d, int64_t ldx, int k,
-                   WsView v, int32_t *__restrict__ lab_out, double *acc,
-                   int amode, int64_t base, int nseg, int wave_all) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int dp = (int)round_up(d, 4);
-  // (fp32 centres: global, scalar loads in resolve_lane)
-  double *lds_acc = (double *)smem;
-  __shared__ unsigned long long blk_count;
-  // per wave: samples stage 1 left undecided, resolved 64 at a time (a
-  // lone stage-2 lane would otherwise hold its whole wave for a second pass)
-  __shared__ int2 dlist[BLOCK / 64][128];
-  if (threadIdx.x == 0) blk_count = 0;
-  if (amode & AM_INLDS) zero_lds_acc(lds_acc, k, d);
-  const float cm =
-      (float)__longlong_as_double((long long)v.hdr->cmax_bits) * 1.000001f;
-  const AccTarget at = acc_target(amode, lds_acc, acc, k, d);
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  unsigned long long mine = 0;
-  int2 *dl = dlist[threadIdx.x >> 6];
-  int dcnt = 0;  // wave-uniform
-  auto stage2 = [&](int2 it) {
-    resolve_lane<MAXD, VEC, TX>(X, ldx, d, k, base + it.x, it.y, v.c32,
-                                v.cn32, dp,
-                                cm, v.ct64, lab_out, amode, at);
-  };
-  // wave_all: the samples go to the global list that k_recheck_wave
-  // resolves a wave per sample (v.smoved as (offset, prev) pairs; the
-  // per-wave LDS list only takes what overflows it).  Otherwise stage 1 runs
-  // here lane per sample and its leftovers are resolved 64 at a time (a long
-  // list holds many of them: a wave per sample cost 0.7 ms per C2 iteration)
-  int2 *s2l = (int2 *)v.smoved;
-  const uint32_t s2cap = (uint32_t)std::min<int64_t>(v.nq / 2, INT32_MAX);
-#if DKM_LIST_SPREAD
-  // (segment, 64-sample batch) pairs dealt round-robin over all waves, batch
-  // index major: every resident wave gets work and the segments' row loads
-  // overlap across waves.  Wave-uniform loop; empty batches are skipped.
-  for (int64_t L = wv; L < (int64_t)nseg * (TL_CAP / 64); L += nwv) {
-    const int64_t sg = L % nseg;
-    const int t0 = (int)(L / nseg) * 64;
-    const int cnt = v.tcount[sg];
-    if (t0 == 0) mine += cnt;
-    if (t0 >= cnt) continue;
-    const int2 *e = v.tlist + sg * TL_CAP;
-    {
-#else
-  for (int64_t sg = wv; sg < nseg; sg += nwv) {
-    const int cnt = v.tcount[sg];
-    mine += cnt;
-    const int2 *e = v.tlist + sg * TL_CAP;
-    for (int t0 = 0; t0 < cnt; t0 += 64) {
-#endif
-      int2 it = make_int2(0, 0);
-      bool ok = true;
-      if (t0 + lane < cnt) {
-        it = e[t0 + lane];
-        // wave_all (short lists): every sample straight to k_recheck_wave
-        ok = !wave_all &&
-             resolve_lane<MAXD, VEC, TX, true>(X, ldx, d, k, base + it.x,
-                                               it.y, v.c32, v.cn32, dp, cm,
-                                               v.ct64, lab_out, amode, at);
-      }
-      unsigned long long m = __ballot(!ok);
-      if (m && wave_all) {
-        uint32_t pos = 0;
-        if (lane == 0) pos = atomicAdd(&v.hdr->s2count, (uint32_t)__popcll(m));
-        pos = (uint32_t)__shfl((int)pos, 0, 64);
-        const uint32_t p = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (!ok && p < s2cap) s2l[p] = it;
-        m = __ballot(!ok && p >= s2cap);   // the rest: this wave, stage 2
-        ok = ok || p < s2cap;
-      }
-      if (!ok) dl[dcnt + __popcll(m & ((1ull << lane) - 1))] = it;
-      dcnt += __popcll(m);
-      if (dcnt >= 64) {
-        wave_lds_sync();
-        stage2(dl[lane]);
-        const int rem = dcnt - 64;
-        const int2 tail = lane < rem ? dl[64 + lane] : make_int2(0, 0);
-        wave_lds_sync();
-        if (lane < rem) dl[lane] = tail;
-        dcnt = rem;
-      }
-    }
-  }
-  wave_lds_sync();
-  if (lane < dcnt) stage2(dl[lane]);
-  recheck_finish_count(mine, &blk_count, v);
-  if (amode & AM_INLDS) flush_lds_acc(lds_acc, acc, k, d);
-}
-
-// k_recheck_list's stage-2 samples (fp32 stage 1 could not decide them),
-// one wave per sample: lanes over centres (resolve_wave), so a sample with
-// many candidates no longer holds a lane -- and its wave -- for a walk over
-// every centre with one exact distance after another (the 1-4 ms spikes of
-// the steady C3 iterations).  Sums by global fp64 atomics (rare samples).
-template <int MAXD, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_wave(const TX *__restrict__ X, int d, int64_t ldx, int k,
-                   WsView v, int32_t *__restrict__ lab_out, double *acc,
-                   int amode, int64_t base) {
-  const uint32_t cap = (uint32_t)std::min<int64_t>(v.nq / 2, INT32_MAX);
-  const uint32_t cnt = min(v.hdr->s2count, cap);
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  if (wv >= cnt) return;
-  const int dp = (int)round_up(d, 4);
-  const float cm =
-      (float)__longlong_as_double((long long)v.hdr->cmax_bits) * 1.000001f;
-  const int am = amode & ~AM_INLDS;
-  const AccTarget at = acc_target(am, nullptr, acc, k, d);
-  const int2 *s2l = (const int2 *)v.smoved;
-  for (int64_t r = wv; r < cnt; r += nwv) {
-    const int2 it = s2l[r];
-    resolve_wave<MAXD, TX>(X, ldx, d, k, base + it.x, it.y, v.c32, v.cn32,
-                           dp, cm, v.ct64, lab_out, am, at);
-  }
-}
-
-template <bool SMALL, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_exact(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
-                    int k, WsView v, int32_t *__restrict__ lab_out,
-                    double *acc, int amode, int64_t base) {
-  if (v.hdr->qcount == 0) return;  // the screen resolved everything
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  double *lds_acc = smem;
-  __shared__ unsigned long long blk_count;
-  if (threadIdx.x == 0) blk_count = 0;
-  if (amode & AM_INLDS) zero_lds_acc(lds_acc, k, d);
-  const AccTarget at = acc_target(amode, lds_acc, acc, k, d);
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  unsigned long long mine = 0;
-  for (int64_t c0 = base + wv * 64; c0 < n; c0 += nwv * 64) {
-    const int64_t li = c0 + lane;
-    const int lv = li < n ? lab_out[li] : 0;
-    unsigned long long mask = __ballot(lv < 0);
-    mine += __popcll(mask);
-    while (mask) {
-      const int bit = __ffsll((long long)mask) - 1;
-      mask &= mask - 1;
-      const int64_t i = c0 + bit;
-      const int prev = -__shfl(lv, bit, WAVE) - 2;
-      const TX *xr = X + i * ldx;
-      double best = INFINITY;
-      int bi = 0x7fffffff;  // lanes without a centre never win
-      for (int jc = lane; jc < k; jc += 64) {
-        const SqDiffT<TX> f{xr, v.ct64 + jc, ct_ld(k)};
-        const double dist =
-            argmin_key(sqrt(SMALL ? pw_leaf(f, 0, d) : pw_sum(f, d)));
-        if (dist < best || bi == 0x7fffffff) {
-          best = dist;
-          bi = jc;
-        }
-      }
-      wave_argmin(best, bi);
-      if (lane == 0) lab_out[i] = bi;
-      recheck_accumulate(amode, at, xr, d, bi, prev, lane);
-    }
-  }
-  recheck_finish_count(mine, &blk_count, v);
-  if (amode & AM_INLDS) flush_lds_acc(lds_acc, acc, k, d);
-}
 
 __global__ void k_add(double *__restrict__ y, const double *__restrict__ x,
                       int64_t n, int32_t *nz) {
@@ -3023,11 +2284,6 @@ static unsigned grid_for(int64_t n, const void *kern, int block, size_t lds) {
   return (unsigned)std::max<int64_t>(1, std::min(need, cap));
 }
 
-// acc_kind: 0 = none (predict), 1 = full accumulation, 2 = delta
-static int acc_mode(int acc_kind, bool lds_fits) {
-  if (acc_kind == 0) return AM_NONE;
-  return AM_ON | (acc_kind == 2 ? AM_DELTA : 0) | (lds_fits ? AM_INLDS : 0);
-}
 
 template <class TX>
 static int launch_exact(const TX *X, int64_t n, int d, int64_t ldx,
@@ -3336,11 +2592,11 @@ static int launch_screen_nks(const TX *X, int64_t end, int d, int64_t ldx,
 #define DKM_SCREEN_CASE(NKS, NB)                                             \
   case NKS:                                                                  \
     return chb ? ((use_list & 2)                                             \
-                      ? launch_screen_t<PREC, NKS, DKM_NB_CHUNK, VEC, TX,    \
+                      ? launch_screen_t<PREC, NKS, NB_CHUNK, VEC, TX,        \
                                         true, true>(                         \
                             X, end, d, ldx, k, v, lab_out, acc, amode, base, \
                             lds, use_list, chb, s, nseg)                     \
-                      : launch_screen_t<PREC, NKS, DKM_NB_CHUNK, VEC, TX,    \
+                      : launch_screen_t<PREC, NKS, NB_CHUNK, VEC, TX,        \
                                         true>(                               \
                             X, end, d, ldx, k, v, lab_out, acc, amode, base, \
                             lds, use_list, chb, s, nseg))                    \
@@ -3348,7 +2604,7 @@ static int launch_screen_nks(const TX *X, int64_t end, int d, int64_t ldx,
                      X, end, d, ldx, k, v, lab_out, acc, amode, base, lds,   \
                      use_list, chb, s, nseg);
   switch (dpad32(d) / 32) {
-    DKM_SCREEN_CASE(1, DKM_NB1)
+    DKM_SCREEN_CASE(1, NB1)
     DKM_SCREEN_CASE(2, 1)
     DKM_SCREEN_CASE(3, 1)
     DKM_SCREEN_CASE(4, 1)
@@ -3357,120 +2613,6 @@ static int launch_screen_nks(const TX *X, int64_t end, int d, int64_t ldx,
   return fail(DKM_E_ARG, "screen: d too large");
 }
 
-template <int MAXD, bool VEC, class TX>
-static void launch_recheck_lane_t(unsigned g, size_t lds, hipStream_t s,
-                                  const TX *X, int64_t end, int d,
-                                  int64_t ldx, int k, const WsView &v,
-                                  int32_t *lab_out, double *acc, int amode,
-                                  int64_t base) {
-  k_recheck_lane<MAXD, VEC, TX><<<g, BLOCK, lds, s>>>(X, end, d, ldx, k, v,
-                                                       lab_out, acc, amode,
-                                                       base);
-}
-
-template <int MAXD, class TX>
-static const void *recheck_lane_fn(bool vec) {
-  return vec ? (const void *)k_recheck_lane<MAXD, true, TX>
-             : (const void *)k_recheck_lane<MAXD, false, TX>;
-}
-
-template <class TX>
-static int launch_recheck(const TX *X, int64_t end, int d, int64_t ldx, int k,
-                          const WsView &v, int32_t *lab_out, double *acc,
-                          int acc_kind, bool vec, int64_t base,
-                          hipStream_t s) {
-  const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
-  const size_t fb = recheck_lane_lds(k, d);
-  const bool lane = d <= 128 && fb <= LDS_BUDGET;
-  const int maxd = d <= 32 ? 32 : d <= 64 ? 64 : 128;
-  const size_t fixed = lane ? fb : 0;
-  const int amode = acc_mode(acc_kind, fixed + a_bytes <= LDS_BUDGET);
-  const size_t lds = fixed + ((amode & AM_INLDS) ? a_bytes : 0);
-  const bool small = d <= 128;
-  const void *kf =
-      !lane   ? (small ? (const void *)k_recheck_exact<true, TX>
-                       : (const void *)k_recheck_exact<false, TX>)
-      : maxd == 32 ? recheck_lane_fn<32, TX>(vec)
-      : maxd == 64 ? recheck_lane_fn<64, TX>(vec)
-                   : recheck_lane_fn<128, TX>(vec);
-  const int per_cu = resident_blocks(kf, BLOCK, lds);
-  const int64_t waves = (end - base + 3 + (lane ? 255 : 63)) / (lane ? 256 : 64);
-  const unsigned g = (unsigned)std::max<int64_t>(
-      1, std::min<int64_t>((int64_t)dev_info().cus * per_cu,
-                           (waves + BLOCK / 64 - 1) / (BLOCK / 64)));
-  if (lane) {
-#define DKM_RL(M)                                                            \
-  (vec ? launch_recheck_lane_t<M, true, TX>(g, lds, s, X, end, d, ldx, k, v, \
-                                            lab_out, acc, amode, base)       \
-       : launch_recheck_lane_t<M, false, TX>(g, lds, s, X, end, d, ldx, k,   \
-                                             v, lab_out, acc, amode, base))
-    if (maxd == 32)
-      DKM_RL(32);
-    else if (maxd == 64)
-      DKM_RL(64);
-    else
-      DKM_RL(128);
-#undef DKM_RL
-  } else if (small) {
-    k_recheck_exact<true, TX><<<g, BLOCK, lds, s>>>(X, end, d, ldx, k, v,
-                                                     lab_out, acc, amode, base);
-  } else {
-    k_recheck_exact<false, TX><<<g, BLOCK, lds, s>>>(X, end, d, ldx, k, v,
-                                                      lab_out, acc, amode, base);
-  }
-  return check_launch("exact re-check");
-}
-
-template <int MAXD, bool VEC, class TX>
-static int launch_list_t(const TX *X, int d, int64_t ldx, int k,
-                         const WsView &v, int32_t *lab_out, double *acc,
-                         int amode, int64_t base, int nseg, size_t lds,
-                         hipStream_t s, bool wave_all) {
-  const void *kf = (const void *)k_recheck_list<MAXD, VEC, TX>;
-  const int per_cu = resident_blocks(kf, BLOCK, lds);
-  const int64_t units = DKM_LIST_SPREAD ? (int64_t)nseg * (TL_CAP / 64) : nseg;
-  const int64_t g = std::max<int64_t>(
-      1, std::min<int64_t>((int64_t)dev_info().cus * per_cu,
-                           (units + BLOCK / 64 - 1) / (BLOCK / 64)));
-  if (hipMemsetAsync(&v.hdr->s2count, 0, 4, s) != hipSuccess)
-    return fail(DKM_E_LAUNCH, "list re-check: counter reset");
-  k_recheck_list<MAXD, VEC, TX><<<(unsigned)g, BLOCK, lds, s>>>(
-      X, d, ldx, k, v, lab_out, acc, amode, base, nseg, wave_all ? 1 : 0);
-  if (int r = check_launch("list re-check")) return r;
-  if (!wave_all) return 0;
-  k_recheck_wave<MAXD, TX><<<(unsigned)(dev_info().cus * 4), BLOCK, 0, s>>>(
-      X, d, ldx, k, v, lab_out, acc, amode, base);
-  return check_launch("list re-check (wave per sample)");
-}
-
-// Can the listed samples be resolved lane-per-sample (k_recheck_list)?
-static bool list_ok(int64_t k, int64_t d) {
-  return d <= 128 && recheck_lane_lds(k, d) <= LDS_BUDGET;
-}
-
-// wave_all: the list is short (a re-screen's leftovers): every sample goes
-// to k_recheck_wave (a wave per sample, its latency spread over the chip)
-// instead of lane-per-sample stage 1, whose per-wave walk over all k centres
-// costs ~1 ms whatever the list's length.
-template <class TX>
-static int launch_list(const TX *X, int d, int64_t ldx, int k,
-                       const WsView &v, int32_t *lab_out, double *acc,
-                       int acc_kind, bool vec, int64_t base, int nseg,
-                       hipStream_t s, bool wave_all = false) {
-  const size_t fb = 0;  // centres are read from global (scalar loads)
-  const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
-  const int amode = acc_mode(acc_kind, fb + a_bytes <= LDS_BUDGET);
-  const size_t lds = fb + ((amode & AM_INLDS) ? a_bytes : 0);
-  const int maxd = d <= 32 ? 32 : d <= 64 ? 64 : 128;
-#define DKM_LL(M)                                                            \
-  (vec ? launch_list_t<M, true, TX>(X, d, ldx, k, v, lab_out, acc, amode,    \
-                                    base, nseg, lds, s, wave_all)            \
-       : launch_list_t<M, false, TX>(X, d, ldx, k, v, lab_out, acc, amode,   \
-                                     base, nseg, lds, s, wave_all))
-  const int r = maxd == 32 ? DKM_LL(32) : maxd == 64 ? DKM_LL(64) : DKM_LL(128);
-#undef DKM_LL
-  return r;
-}
 
 
 // ---------------------------------------------------------------------------
@@ -3583,13 +2725,13 @@ static int launch_label_sums(const TX *X, int64_t lo, int64_t hi, int d,
 
 // Sums from finished labels: the counting sort + segmented sums of
 // dkm_sums.hip when its scratch holds the range (k <= SORT_KMAX), else
-// k_label_sums.  AB_LABEL_SUMS (A/B builds) forces k_label_sums.
+// k_label_sums.
 template <class TX>
 static int launch_post_sums(const TX *X, int64_t lo, int64_t hi, int d,
                             int64_t ldx, const int32_t *lab,
                             const int32_t *prev, int k, double *acc,
                             const WsView &v, hipStream_t s) {
-  if (!AB_LABEL_SUMS && sorted_sums_ok(k, hi - lo, v))
+  if (sorted_sums_ok(k, hi - lo, v))
     return sorted_sums<TX>(X, lo, hi, d, ldx, lab, prev, k, acc, v, s);
   return launch_label_sums<TX>(X, lo, hi, d, ldx, lab, prev, k, acc, s);
 }
@@ -3740,15 +2882,289 @@ __global__ void __launch_bounds__(256)
     lab_out[list[r].x] = lab[r];
 }
 
+// launch_screen's inputs besides the data.
+struct ScreenOpts {
+  bool nohint = false;         // DKM_MODE_NOHINT: the labels are poor hints
+  bool force_b1 = false;       // DKM_MODE_B1: k_screen_b1, not k_screen_b2
+  bool sub = false;            // a re-screen's call, on gathered rows
+  bool transl = false;         // DKM_MODE_TRANSLATE
+  void *build_img = nullptr;   // DKM_IMAGE_BUILD: the split image to write
+  const BoundsHost *bnds = nullptr;  // per-row bounds
+};
+
+// What one launch_screen call runs, from its shape alone (plan_screen makes
+// no HIP call).  The r == 1 fall-throughs (k_screen_b2 -> k_screen_b1, the
+// listing w32 pass -> the plain one, c32 -> k_screen) are taken at launch.
+enum class Screen { B1, W32, F32, B3 };
+struct ScreenPlan {
+  Screen screen;
+  bool vec;         // 16-B rows: d % 8 == 0, aligned X and stride
+  int64_t chunk;    // rows per pass of the loop
+  int chb;          // k_screen's LDS chunk, in 16-centre blocks (0: resident)
+  size_t fb, lds;   // LDS: the fragments; with the sums that fit beside them
+  bool post;        // the screen writes labels only: sums from the labels
+  bool premoved;    // ... the moved rows listed by the sorted image's sync
+  bool mlist;       // the w32 threshold pass lists the rows it moves
+  bool c2;          // k_screen's two-candidate list (T3) + k_cand2
+  bool c32;         // try k_screen_c32 before k_screen
+  bool rescreen;    // re-screen this call's re-check list
+  bool fuse_build;  // the full-sums w32 pass writes the split image
+  int hint;         // single product: the incoming labels seed the pass
+  int use_list, skind, amode;
+};
+
+static ScreenPlan plan_screen(int prec, const void *X, size_t tx, int64_t n,
+                              int d, int64_t ldx, int k, const WsView &v,
+                              const int32_t *labels, int acc_kind,
+                              const XImage &img, const ScreenOpts &o) {
+  ScreenPlan p;
+  const int64_t nq = std::min<int64_t>(v.nq, INT32_MAX);
+  // DKM_MODE_TRANSLATE (a fit's first assignment against crowded initial
+  // centres): many samples keep two or more candidates, so the call runs in
+  // row chunks that keep the per-wave lists within their capacity
+  p.chunk = labels ? (o.transl ? std::min<int64_t>(n, TRANSL_CHUNK) : n) : nq;
+  p.vec = (d % 8 == 0) && (ldx % (16 / (int64_t)tx) == 0) &&
+          (((uintptr_t)X % 16) == 0);
+  // single-product screen: labels only, so the sums must come from
+  // k_label_sums (full sums, or delta against a copy of the old labels)
+  const bool b1 = prec == P_B1 && v.b1frag && p.vec &&
+                  (int64_t)32 * ldx * (int64_t)tx < (1ll << 31) &&
+                  (acc_kind == 0 || acc_kind == 1 || (labels && nq >= n));
+  if (prec == P_B1 && !b1) prec = P_B3;
+  // d <= 32 bf16x3 with the 32x32x16 fragments resident: k_screen_w32
+  const size_t fb32 = (size_t)(kpad32(k) / 32) * (4096 + 128);
+  // (a bounds call reads X only through the list form, which also takes
+  // rows that are not 16-B pieces: d % 8 != 0 or unaligned X)
+  const bool w32 = prec == P_B3 && d <= 32 && (p.vec || o.bnds) &&
+                   fb32 <= LDS_BUDGET &&
+                   (int64_t)32 * ldx * (int64_t)tx < (1ll << 31);
+  p.screen = b1 ? Screen::B1
+             : w32 ? Screen::W32
+             : prec == P_F32 ? Screen::F32
+                             : Screen::B3;
+  p.chb = w32 ? 0 : screen_chunk_blocks(k, d);
+  p.fb = w32 ? fb32
+         : p.chb ? (size_t)p.chb * ((dpad32(d) / 32) * 2048 + 64)
+                 : screen_lds_fixed(k, d);
+  const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
+  // sums that do not fit block-private LDS: the screen writes labels only
+  // and k_label_sums accumulates from them (delta: against a copy of the
+  // previous labels in the label scratch)
+  const bool lds_fits = p.fb + a_bytes <= LDS_BUDGET;
+  p.post = acc_kind != 0 && (!lds_fits || b1) &&
+           (acc_kind == 1 || (labels && nq >= n));
+  // the sorted image's incremental sums: the label sync lists the moved
+  // rows with their previous labels (in the queue scratch), so neither a
+  // copy of the labels nor a scan for changes is needed
+  p.premoved = p.post && acc_kind == 2 && b1 && img.kind == IMG_SORTED &&
+               p.chunk >= n && sorted_sums_ok(k, n, v);
+  p.skind = p.post ? 0 : acc_kind;
+  p.amode = acc_mode(p.skind, lds_fits);
+  p.lds = p.fb + ((p.amode & AM_INLDS) ? a_bytes : 0);
+  p.use_list = list_ok(k, d) ? 1 : 0;
+  // the chunked bf16x3 screen's two-candidate list (T3 in k_screen): labels-
+  // only launches whose rows k_cand2 can take (d % 8 == 0, d <= 128)
+  // (sub: this call is a re-screen's, on gathered rows)
+  p.c2 = o.sub && !b1 && !w32 && p.chb && prec == P_B3 &&
+         p.amode == AM_NONE && v.clist && p.vec && d % 8 == 0 && d >= 8 &&
+         d <= 128;
+  // the chunked labels-only bf16x3 screen in 32x32x16 form (32 < d <= 64)
+  p.c32 = p.chb && p.vec && p.amode == AM_NONE && !o.sub && d > 32 && d <= 64;
+  // the re-screen of this call's re-check list: labels-only screens whose
+  // gathered rows the chunked bf16x3 screen with its two-candidate list
+  // takes (c2's conditions on the gathered, packed rows)
+  p.rescreen = !o.sub && v.rlist && p.amode == AM_NONE && p.use_list &&
+               screen_chunk_blocks(k, d) > 0 &&
+               (b1 || (prec == P_B3 && p.chb && !w32)) && d % 8 == 0 &&
+               d >= 8 && d <= 128;
+  // DKM_IMAGE_BUILD: the split image written by this call's full-sums w32
+  // pass over X (one launch from row 0), else built first
+  p.fuse_build = o.build_img && w32 && am_full(p.amode) &&
+                 img.kind == IMG_SPLIT && p.chunk >= n;
+  // the d <= 32 image threshold pass of a delta call: the rows it moves
+  // are listed and summed by sorted_sums_moved after the re-checks (a
+  // moved row's fp64 load and +-x adds inside the screen stalled its wave:
+  // C2's iteration 2, 4.7 % of the rows moving, took 7.2 ms against 3.7)
+  p.mlist = w32 && acc_kind == 2 && !p.post && labels && p.chunk >= n &&
+            img.tiles && img.kind == IMG_SPLIT && !o.build_img &&
+            (int64_t)n <= nq && sorted_sums_ok(k, n, v);
+  // the incoming labels (previous iteration) seed the single product's
+  // threshold pass (NOHINT: the caller knows them to be poor, e.g. labels of
+  // the initial centres -- the top-3 pass runs directly)
+  p.hint = labels && acc_kind != 0 && !o.nohint ? 1 : 0;
+  return p;
+}
+
+template <class TX>
+static int rescreen_list(const TX *X, int d, int64_t ldx, const double *C,
+                         int k, const WsView &v, int32_t *lab_out,
+                         int64_t base, int nseg, hipStream_t s);
+
+// Screen + exact re-check over [0, n).  Labels go to `labels` when given,
+// else to the workspace scratch (queue region), in chunks of its capacity.
 template <class TX>
 static int launch_screen(int prec, const TX *X, int64_t n, int d,
                          int64_t ldx, const double *C, int k, const WsView &v,
-                         size_t wsb, int32_t *labels, double *acc,
-                         int acc_kind, hipStream_t s, XImage img,
-                         bool nohint = false, bool force_b1 = false,
-                         void *build_img = nullptr, bool sub = false,
-                         bool transl = false,
-                         const BoundsHost *bnds = nullptr);
+                         int32_t *labels, double *acc, int acc_kind,
+                         hipStream_t s, XImage img, const ScreenOpts &o) {
+  if (!labels && std::min<int64_t>(v.nq, INT32_MAX) < 1)
+    return fail(DKM_E_WORKSPACE, "screen: no label scratch");
+  const ScreenPlan p = plan_screen(prec, X, sizeof(TX), n, d, ldx, k, v,
+                                   labels, acc_kind, img, o);
+  const bool b1 = p.screen == Screen::B1;
+  if (img.kind == IMG_SORTED && !b1)
+    return fail(DKM_E_ARG, "screen: the sorted image needs the single-product "
+                           "screen (16-B aligned rows)");
+  const int32_t *prevbuf = nullptr;
+  if (p.post && acc_kind == 2 && !p.premoved) {
+    if (hipMemcpyAsync(v.queue, labels, (size_t)n * 4,
+                       hipMemcpyDeviceToDevice, s) != hipSuccess)
+      return fail(DKM_E_LAUNCH, "screen: label copy");
+    prevbuf = v.queue;
+  }
+  if (o.build_img && !p.fuse_build) {
+    if (int r = launch_x_image<TX>(X, n, d, ldx, img.kind, o.build_img,
+                                   dev_info().cus, s))
+      return r;
+  }
+  if (p.mlist && hipMemsetAsync(&v.hdr->nmoved, 0, 4, s) != hipSuccess)
+    return fail(DKM_E_LAUNCH, "screen: memset");
+  // per-row bounds: the image threshold pass (with its moved-row list) only
+  if (o.bnds && !(p.mlist && v.prevc && bounds_shape(k, d)))
+    return fail(DKM_E_ARG, "bounds: the call does not take the d <= 32 "
+                           "image threshold pass (dkm_bounds_ok, a built "
+                           "split image, n label slots in the workspace)");
+  bool mlist = p.mlist;  // (a fall-through below may drop it)
+  for (int64_t base = 0; base < n; base += p.chunk) {
+    const int64_t end = std::min(n, base + p.chunk);
+    int32_t *lab_out = labels ? labels : v.queue - base;
+    int r = 0, nseg = 0;
+    switch (p.screen) {
+    case Screen::B1:
+      r = o.force_b1 ? 1
+                     : launch_screen_b2<TX>(X, end, d, ldx, k, v, lab_out,
+                                            base, p.hint, dev_info().cus, s,
+                                            &nseg, img, o.transl);
+      if (r == 1 && img.kind == IMG_SORTED)
+        return fail(DKM_E_ARG, "screen: the sorted image needs k_screen_b2");
+      if (r == 1)
+        r = launch_screen_b1<TX>(X, end, d, ldx, k, v, lab_out, base, p.hint,
+                                 s, &nseg);
+      if (r) return r;
+      r = launch_cand2<TX>(X, d, ldx, C, v, lab_out, base, nseg, s);
+      if (!r && p.hint)
+        r = launch_candn<TX>(X, d, ldx, C, v, lab_out, base, nseg, s);
+      break;
+    case Screen::W32:
+      if (o.bnds) {
+        // the bounds pass lists the rows with !(u < l) in v.sitems; then the
+        // list form and the image form of the screen, of which the device
+        // count of active rows lets one run (an init call: the image form)
+        const BndArgs ba{o.bnds->ub, o.bnds->lb, v.sitems, &v.hdr->nactive,
+                         (uint32_t)bounds_list_cap(n, bounds_list_frac()),
+                         o.bnds->init ? 0 : 1,
+                         p.vec ? 1 : 0};
+        int ns2 = 0;
+        if (ba.upd) {
+          if (hipMemsetAsync(&v.hdr->nactive, 0, 4, s) != hipSuccess ||
+              hipMemsetAsync(v.tcount, 0, (size_t)TL_SEGS * 4, s) !=
+                  hipSuccess)
+            return fail(DKM_E_LAUNCH, "bounds: memset");
+          const unsigned gb = (unsigned)std::max<int64_t>(
+              1, std::min<int64_t>((n + 1023) / 1024,
+                                   (int64_t)dev_info().cus * 8));
+          k_bounds_pass<<<gb, 256, 0, s>>>(o.bnds->ub, o.bnds->lb, lab_out, n,
+                                           k, v, v.sitems, ba.thresh);
+          if ((r = check_launch("bounds pass"))) return r;
+          r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                    AM_DELTA | AM_MLIST, base, p.fb,
+                                    p.use_list, s, &ns2, img, false, &ba,
+                                    true);
+        }
+        if (!r)
+          r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                    AM_DELTA | AM_MLIST, base, p.fb,
+                                    p.use_list, s, &nseg, img, false, &ba,
+                                    false);
+        if (r == 1)
+          return fail(DKM_E_ARG, "bounds: the screens do not fit LDS");
+        nseg = std::max(nseg, ns2);
+        // the centres these bounds hold for: the next call's drift
+        if (!r && hipMemcpyAsync(v.prevc, C, (size_t)k * d * 8,
+                                 hipMemcpyDeviceToDevice, s) != hipSuccess)
+          return fail(DKM_E_LAUNCH, "bounds: centre copy");
+        break;
+      }
+      r = mlist ? launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                        AM_DELTA | AM_MLIST, base, p.fb,
+                                        p.use_list, s, &nseg, img)
+                : 1;
+      if (r == 1) {
+        mlist = false;
+        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc, p.amode,
+                                  base, p.lds, p.use_list, s, &nseg, img,
+                                  p.fuse_build);
+      }
+      break;
+    case Screen::F32:
+      r = p.vec ? launch_screen_nks<P_F32, true, TX>(
+                      X, end, d, ldx, k, v, lab_out, acc, p.amode, base,
+                      p.lds, p.use_list, p.chb, s, &nseg)
+                : launch_screen_nks<P_F32, false, TX>(
+                      X, end, d, ldx, k, v, lab_out, acc, p.amode, base,
+                      p.lds, p.use_list, p.chb, s, &nseg);
+      break;
+    case Screen::B3:
+      r = p.c32 ? launch_screen_c32<TX>(X, end, d, ldx, k, v, lab_out, base,
+                                        p.use_list, s, &nseg)
+                : 1;
+      if (r == 1)
+        r = p.vec ? launch_screen_nks<P_B3, true, TX>(
+                        X, end, d, ldx, k, v, lab_out, acc, p.amode, base,
+                        p.lds, p.use_list | (p.c2 ? 2 : 0), p.chb, s, &nseg)
+                  : launch_screen_nks<P_B3, false, TX>(
+                        X, end, d, ldx, k, v, lab_out, acc, p.amode, base,
+                        p.lds, p.use_list, p.chb, s, &nseg);
+      break;
+    }
+    if (r) return r;
+    if (p.c2 && (r = launch_cand2<TX>(X, d, ldx, C, v, lab_out, base,
+                                      std::min(nseg, B1_SEGS), s)))
+      return r;
+    if (p.rescreen &&
+        (r = rescreen_list<TX>(X, d, ldx, C, k, v, lab_out, base, nseg, s)))
+      return r;
+    if ((p.use_list || b1) &&
+        (r = launch_list<TX>(X, d, ldx, k, v, lab_out, acc, p.skind, p.vec,
+                             base, nseg, s, o.sub)))
+      return r;
+    if ((r = launch_recheck<TX>(X, end, d, ldx, k, v, lab_out, acc, p.skind,
+                                p.vec, base, s)))
+      return r;
+    // the sorted image's label copy: the rows the re-checks decided (and,
+    // premoved, the list of rows that moved)
+    if (b1 && (r = launch_plab_sync(img, n, k, labels, dev_info().cus, s,
+                                    p.premoved ? v.smoved : nullptr,
+                                    p.premoved ? &v.hdr->nmoved : nullptr,
+                                    p.premoved ? v.queue : nullptr)))
+      return r;
+    if (mlist) {
+      r = launch_moved_sums<TX>(X, ldx, d, k, lab_out, acc, v, s);
+      if (r == 1)
+        r = sorted_sums_moved<TX>(X, n, d, ldx, lab_out, v.queue, k, acc, v,
+                                  s);
+      if (r) return r;
+    } else if (p.premoved) {
+      if ((r = sorted_sums_moved<TX>(X, n, d, ldx, lab_out, v.queue, k, acc,
+                                     v, s)))
+        return r;
+    } else if (p.post && (r = launch_post_sums<TX>(X, base, end, d, ldx,
+                                                   lab_out, prevbuf, k, acc,
+                                                   v, s)))
+      return r;
+  }
+  return 0;
+}
 
 // The samples a screen left to the exact re-check (its per-wave lists) are
 // gathered, RS_ROWS at a time, and screened again by the chunked bf16x3
@@ -3764,7 +3180,7 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
 // read per call (the list's length sizes the gathered chunks).
 template <class TX>
 static int rescreen_list(const TX *X, int d, int64_t ldx, const double *C,
-                         int k, const WsView &v, size_t wsb, int32_t *lab_out,
+                         int k, const WsView &v, int32_t *lab_out,
                          int64_t base, int nseg, hipStream_t s) {
   nseg = std::min(nseg, TL_SEGS);
   if (nseg <= 0) return 0;
@@ -3786,6 +3202,7 @@ static int rescreen_list(const TX *X, int d, int64_t ldx, const double *C,
   k_list_compact<<<(unsigned)std::min<int64_t>((nseg + 3) / 4, cus * 8), 256,
                    0, s>>>(v.tlist, v.tcount, v.rprefix, nseg, v.rlist);
   if (int r = check_launch("re-screen: compact")) return r;
+  const ScreenOpts gathered{.sub = true};
   for (int64_t c0 = 0; c0 < (int64_t)tot; c0 += RS_ROWS) {
     const int m = (int)std::min<int64_t>(RS_ROWS, (int64_t)tot - c0);
     const unsigned g = (unsigned)std::max<int64_t>(
@@ -3794,10 +3211,10 @@ static int rescreen_list(const TX *X, int d, int64_t ldx, const double *C,
                                         (TX *)v.rx);
     if (int r = check_launch("re-screen: gather")) return r;
     if (int r = launch_screen<TX>(P_B3, (const TX *)v.rx, m, d, d, C, k, v,
-                                  wsb, v.rlab, nullptr, 0, s,
+                                  v.rlab, nullptr, 0, s,
                                   XImage{nullptr, nullptr, IMG_NONE, nullptr,
                                          nullptr},
-                                  false, false, nullptr, true))
+                                  gathered))
       return r;
     k_scatter_labels<<<(unsigned)std::max(1, std::min((m + 255) / 256,
                                                       cus * 8)),
@@ -3810,243 +3227,6 @@ static int rescreen_list(const TX *X, int d, int64_t ldx, const double *C,
   return 0;
 }
 
-// Screen + exact re-check over [0, n).  Labels go to `labels` when given,
-// else to the workspace scratch (queue region), in chunks of its capacity.
-template <class TX>
-static int launch_screen(int prec, const TX *X, int64_t n, int d,
-                         int64_t ldx, const double *C, int k, const WsView &v,
-                         size_t wsb, int32_t *labels, double *acc,
-                         int acc_kind, hipStream_t s, XImage img,
-                         bool nohint, bool force_b1, void *build_img,
-                         bool sub, bool transl, const BoundsHost *bnds) {
-  (void)wsb;
-  const int64_t nq = std::min<int64_t>(v.nq, INT32_MAX);
-  if (!labels && nq < 1)
-    return fail(DKM_E_WORKSPACE, "screen: no label scratch");
-  // DKM_MODE_TRANSLATE (a fit's first assignment against crowded initial
-  // centres): many samples keep two or more candidates, so the call runs in
-  // row chunks that keep the per-wave lists within their capacity
-  const int64_t chunk =
-      labels ? (transl ? std::min<int64_t>(n, TRANSL_CHUNK) : n) : nq;
-  const bool vec = (d % 8 == 0) && (ldx % (16 / (int64_t)sizeof(TX)) == 0) &&
-                   (((uintptr_t)X % 16) == 0);
-  // single-product screen: labels only, so the sums must come from
-  // k_label_sums (full sums, or delta against a copy of the old labels)
-  const bool b1 = prec == P_B1 && v.b1frag && vec &&
-                  (int64_t)32 * ldx * (int64_t)sizeof(TX) < (1ll << 31) &&
-                  (acc_kind == 0 || acc_kind == 1 || (labels && nq >= n));
-  if (prec == P_B1 && !b1) prec = P_B3;
-  if (img.kind == IMG_SORTED && !b1)
-    return fail(DKM_E_ARG, "screen: the sorted image needs the single-product "
-                           "screen (16-B aligned rows)");
-  // d <= 32 bf16x3 with the 32x32x16 fragments resident: k_screen_w32
-  const size_t fb32 = (size_t)(kpad32(k) / 32) * (4096 + 128);
-  // (a bounds call reads X only through the list form, which also takes
-  // rows that are not 16-B pieces: d % 8 != 0 or unaligned X)
-  const bool w32 = prec == P_B3 && d <= 32 && (vec || bnds) &&
-                   fb32 <= LDS_BUDGET &&
-                   (int64_t)32 * ldx * (int64_t)sizeof(TX) < (1ll << 31) &&
-                   !AB_NO_W32;
-  const int chb = w32 ? 0 : screen_chunk_blocks(k, d);
-  const size_t fb = w32 ? fb32
-                    : chb ? (size_t)chb * ((dpad32(d) / 32) * 2048 + 64)
-                          : screen_lds_fixed(k, d);
-  const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
-  // sums that do not fit block-private LDS: the screen writes labels only
-  // and k_label_sums accumulates from them (delta: against a copy of the
-  // previous labels in the label scratch)
-  const bool lds_fits = fb + a_bytes <= LDS_BUDGET;
-  // AB_DELTA_POST: delta sums from k_label_sums even when they fit LDS
-  // (the screen then needs only the fragments' LDS: more blocks per CU)
-  const bool force_post = acc_kind == 2 && AB_DELTA_POST;
-  const bool post = acc_kind != 0 && (!lds_fits || force_post || b1) &&
-                    !AB_NO_POST &&
-                    (acc_kind == 1 || (labels && nq >= n));
-  // the sorted image's incremental sums: the label sync lists the moved
-  // rows with their previous labels (in the queue scratch), so neither a
-  // copy of the labels nor a scan for changes is needed
-  const bool premoved = post && acc_kind == 2 && b1 &&
-                        img.kind == IMG_SORTED && chunk >= n &&
-                        !AB_LABEL_SUMS && sorted_sums_ok(k, n, v);
-  const int32_t *prevbuf = nullptr;
-  if (post && acc_kind == 2 && !premoved) {
-    if (hipMemcpyAsync(v.queue, labels, (size_t)n * 4,
-                       hipMemcpyDeviceToDevice, s) != hipSuccess)
-      return fail(DKM_E_LAUNCH, "screen: label copy");
-    prevbuf = v.queue;
-  }
-  const int skind = post ? 0 : acc_kind;
-  const int amode = acc_mode(skind, lds_fits);
-  const size_t lds = fb + ((amode & AM_INLDS) ? a_bytes : 0);
-  const int use_list = list_ok(k, d) && !AB_NO_LIST ? 1 : 0;
-  // the chunked bf16x3 screen's two-candidate list (T3 in k_screen): labels-
-  // only launches whose rows k_cand2 can take (d % 8 == 0, d <= 128)
-  // (sub: this call is a re-screen's, on gathered rows)
-  const bool c2 = sub && !b1 && !w32 && chb && prec == P_B3 &&
-                  amode == AM_NONE && v.clist && vec && d % 8 == 0 &&
-                  d >= 8 && d <= 128;
-  // the re-screen of this call's re-check list: labels-only screens whose
-  // gathered rows the chunked bf16x3 screen with its two-candidate list
-  // takes (c2's conditions on the gathered, packed rows)
-  const bool rescreen = !sub && v.rlist && amode == AM_NONE && use_list &&
-                        screen_chunk_blocks(k, d) > 0 &&
-                        (b1 || (prec == P_B3 && chb && !w32)) &&
-                        d % 8 == 0 && d >= 8 && d <= 128;
-  // DKM_IMAGE_BUILD: the split image written by this call's full-sums w32
-  // pass over X (one launch from row 0), else built first
-  bool fuse_build = false;
-  if (build_img) {
-    fuse_build = w32 && am_full(amode) && img.kind == IMG_SPLIT && chunk >= n;
-    if (!fuse_build) {
-      if (int r = launch_x_image<TX>(X, n, d, ldx, img.kind, build_img,
-                                     dev_info().cus, s))
-        return r;
-    }
-  }
-  // the d <= 32 image threshold pass of a delta call: the rows it moves
-  // are listed and summed by sorted_sums_moved after the re-checks (a
-  // moved row's fp64 load and +-x adds inside the screen stalled its wave:
-  // C2's iteration 2, 4.7 % of the rows moving, took 7.2 ms against 3.7)
-  bool mlist = w32 && acc_kind == 2 && !post && labels && chunk >= n &&
-               img.tiles && img.kind == IMG_SPLIT && !build_img &&
-               (int64_t)n <= nq && sorted_sums_ok(k, n, v) && !AB_NO_MLIST;
-  if (mlist && hipMemsetAsync(&v.hdr->nmoved, 0, 4, s) != hipSuccess)
-    return fail(DKM_E_LAUNCH, "screen: memset");
-  // per-row bounds: the image threshold pass (with its moved-row list) only
-  if (bnds && !(mlist && v.prevc && bounds_shape(k, d)))
-    return fail(DKM_E_ARG, "bounds: the call does not take the d <= 32 "
-                           "image threshold pass (dkm_bounds_ok, a built "
-                           "split image, n label slots in the workspace)");
-  for (int64_t base = 0; base < n; base += chunk) {
-    const int64_t end = std::min(n, base + chunk);
-    int32_t *lab_out = labels ? labels : v.queue - base;
-    int r, nseg = 0;
-    if (b1) {
-      // the incoming labels (previous iteration) seed the threshold pass
-      // (NOHINT: the caller knows them to be poor, e.g. labels of the
-      // initial centres -- the top-3 pass runs directly)
-      const int hint = labels && acc_kind != 0 && !nohint ? 1 : 0;
-      r = force_b1 ? 1
-                   : launch_screen_b2<TX>(X, end, d, ldx, k, v, lab_out, base,
-                                          hint, dev_info().cus, s, &nseg, img,
-                                          transl);
-      if (r == 1 && img.kind == IMG_SORTED)
-        return fail(DKM_E_ARG, "screen: the sorted image needs k_screen_b2");
-      if (r == 1)
-        r = launch_screen_b1<TX>(X, end, d, ldx, k, v, lab_out, base, hint, s,
-                                 &nseg);
-      if (r) return r;
-      r = launch_cand2<TX>(X, d, ldx, C, v, lab_out, base, nseg, s);
-      if (!r && hint) r = launch_candn<TX>(X, d, ldx, C, v, lab_out, base,
-                                           nseg, s);
-    } else if (w32 && bnds) {
-      // the bounds pass lists the rows with !(u < l) in v.sitems; then the
-      // list form and the image form of the screen, of which the device
-      // count of active rows lets one run (an init call: the image form)
-      const BndArgs ba{bnds->ub, bnds->lb, v.sitems, &v.hdr->nactive,
-                       (uint32_t)bounds_list_cap(n, bounds_list_frac()),
-                       bnds->init ? 0 : 1,
-                       vec ? 1 : 0};
-      int ns2 = 0;
-      r = 0;
-      if (ba.upd) {
-        if (hipMemsetAsync(&v.hdr->nactive, 0, 4, s) != hipSuccess ||
-            hipMemsetAsync(v.tcount, 0, (size_t)TL_SEGS * 4, s) != hipSuccess)
-          return fail(DKM_E_LAUNCH, "bounds: memset");
-        const unsigned gb = (unsigned)std::max<int64_t>(
-            1, std::min<int64_t>((n + 1023) / 1024,
-                                 (int64_t)dev_info().cus * 8));
-        k_bounds_pass<<<gb, 256, 0, s>>>(bnds->ub, bnds->lb, lab_out, n, k, v,
-                                         v.sitems, ba.thresh);
-        if ((r = check_launch("bounds pass"))) return r;
-        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
-                                  AM_DELTA | AM_MLIST, base, fb, use_list, s,
-                                  &ns2, img, false, &ba, true);
-      }
-      if (!r)
-        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
-                                  AM_DELTA | AM_MLIST, base, fb, use_list, s,
-                                  &nseg, img, false, &ba, false);
-      if (r == 1) return fail(DKM_E_ARG, "bounds: the screens do not fit LDS");
-      nseg = std::max(nseg, ns2);
-      // the centres these bounds hold for: the next call's drift
-      if (!r && hipMemcpyAsync(v.prevc, C, (size_t)k * d * 8,
-                               hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(DKM_E_LAUNCH, "bounds: centre copy");
-    } else if (w32) {
-      r = mlist ? launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
-                                        AM_DELTA | AM_MLIST, base, fb,
-                                        use_list, s, &nseg, img)
-                : 1;
-      if (r == 1) {
-        mlist = false;
-        r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc, amode,
-                                  base, lds, use_list, s, &nseg, img,
-                                  fuse_build);
-      }
-    }
-    else if (prec == P_F32)
-      r = vec ? launch_screen_nks<P_F32, true, TX>(X, end, d, ldx, k, v,
-                                                   lab_out, acc, amode, base,
-                                                   lds, use_list, chb, s, &nseg)
-              : launch_screen_nks<P_F32, false, TX>(X, end, d, ldx, k, v,
-                                                    lab_out, acc, amode, base,
-                                                    lds, use_list, chb, s, &nseg);
-    else {
-      // the chunked labels-only bf16x3 screen in 32x32x16 form (32 < d <= 64)
-      const bool c32 = chb && vec && amode == AM_NONE && !sub && d > 32 &&
-                       d <= 64 && !AB_NO_C32;
-      r = c32 ? launch_screen_c32<TX>(X, end, d, ldx, k, v, lab_out, base,
-                                      use_list, s, &nseg)
-              : 1;
-      if (r == 1)
-        r = vec ? launch_screen_nks<P_B3, true, TX>(
-                      X, end, d, ldx, k, v, lab_out, acc, amode, base, lds,
-                      use_list | (c2 ? 2 : 0), chb, s, &nseg)
-                : launch_screen_nks<P_B3, false, TX>(X, end, d, ldx, k, v,
-                                                     lab_out, acc, amode,
-                                                     base, lds, use_list, chb,
-                                                     s, &nseg);
-    }
-    if (r) return r;
-    if (c2 && (r = launch_cand2<TX>(X, d, ldx, C, v, lab_out, base,
-                                    std::min(nseg, B1_SEGS), s)))
-      return r;
-    if (rescreen && (r = rescreen_list<TX>(X, d, ldx, C, k, v, wsb, lab_out,
-                                           base, nseg, s)))
-      return r;
-    if ((use_list || b1) && (r = launch_list<TX>(X, d, ldx, k, v, lab_out,
-                                                  acc, skind, vec, base,
-                                                  nseg, s, sub)))
-      return r;
-    if ((r = launch_recheck<TX>(X, end, d, ldx, k, v, lab_out, acc,
-                                skind, vec, base, s)))
-      return r;
-    // the sorted image's label copy: the rows the re-checks decided (and,
-    // premoved, the list of rows that moved)
-    if (b1 && (r = launch_plab_sync(img, n, k, labels, dev_info().cus, s,
-                                    premoved ? v.smoved : nullptr,
-                                    premoved ? &v.hdr->nmoved : nullptr,
-                                    premoved ? v.queue : nullptr)))
-      return r;
-    if (mlist) {
-      r = launch_moved_sums<TX>(X, ldx, d, k, lab_out, acc, v, s);
-      if (r == 1)
-        r = sorted_sums_moved<TX>(X, n, d, ldx, lab_out, v.queue, k, acc, v,
-                                  s);
-      if (r) return r;
-    } else if (premoved) {
-      if ((r = sorted_sums_moved<TX>(X, n, d, ldx, lab_out, v.queue, k, acc,
-                                     v, s)))
-        return r;
-    } else if (post && (r = launch_post_sums<TX>(X, base, end, d, ldx,
-                                                 lab_out, prevbuf, k, acc, v,
-                                                 s)))
-      return r;
-  }
-  return 0;
-}
-
 // d > 128: the bf16x3 GEMM screen (dkm_gemm.hip), which also resolves the
 // samples it leaves open with the reference arithmetic.  Sums come from k_label_sums (X is read once more,
 // lanes over features) unless the previous labels cannot be kept for a
@@ -4054,11 +3234,10 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
 // changed rows itself with fp64 atomics.
 template <class TX>
 static int launch_gemm(const TX *X, int64_t n, int d, int64_t ldx,
-                       const double *C, int k, const WsView &v, size_t wsb,
+                       const double *C, int k, const WsView &v,
                        int32_t *labels, double *acc, int acc_kind,
                        bool one, const XImage *img, hipStream_t s,
                        const XImage *bimg = nullptr) {
-  (void)wsb;
   const int64_t nq = std::min<int64_t>(v.nq, INT32_MAX);
   if (!labels && nq < 1)
     return fail(DKM_E_WORKSPACE, "gemm: no label scratch");
@@ -4147,7 +3326,7 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
   // the bf16x3 GEMM screen's chunk splits write the single-product image's
   // hi tiles as they convert X (the fit's first iteration; no image pass)
   const bool split_gemm = build && image_kind == IMG_GEMM && labels &&
-      mode == DKM_MODE_SCREEN_BF16X3 && gemm_path(k, d) && !AB_NO_GEMM_BUILD;
+      mode == DKM_MODE_SCREEN_BF16X3 && gemm_path(k, d);
   if (build && !split_w32 && !split_gemm) {
     // no screen writes this kind in its pass: build it first
     if (int r = x_image<TX>(X, n, d, ldx, image_kind, (void *)image,
@@ -4172,7 +3351,7 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
     if (use_img) gimg = x_image_view(image, n, d, IMG_GEMM);
     XImage bimg;
     if (split_gemm) bimg = x_image_view(image, n, d, IMG_GEMM);
-    return launch_gemm<TX>(X, n, (int)d, ldx, C, (int)k, v, wsb, labels, acc,
+    return launch_gemm<TX>(X, n, (int)d, ldx, C, (int)k, v, labels, acc,
                            acc_kind, mode == DKM_MODE_SCREEN_BF16,
                            use_img ? &gimg : nullptr, s,
                            split_gemm ? &bimg : nullptr);
@@ -4193,10 +3372,12 @@ static int assign(const TX *X, int64_t n, int64_t d, int64_t ldx,
     // the translated centres serve the single-product screen without the
     // sorted image (its block skipping reads absolute scores)
     if (image_kind == IMG_SORTED || prec != P_B1) transl = false;
-    return launch_screen<TX>(prec, X, n, (int)d, ldx, C, (int)k, v, wsb,
-                             labels, acc, acc_kind, s, img, nohint, force_b1,
-                             build && split_w32 ? (void *)image : nullptr,
-                             false, transl, bnds);
+    const ScreenOpts o{
+        .nohint = nohint, .force_b1 = force_b1, .transl = transl,
+        .build_img = build && split_w32 ? (void *)image : nullptr,
+        .bnds = bnds};
+    return launch_screen<TX>(prec, X, n, (int)d, ldx, C, (int)k, v, labels,
+                             acc, acc_kind, s, img, o);
   }
   return fail(DKM_E_ARG, std::string(who) + ": bad mode");
 }
@@ -4344,8 +3525,7 @@ int dkm_x_image_kind(int64_t k, int64_t d, int mode) {
                ? IMG_SINGLE
                : IMG_NONE;
   if (mode == DKM_MODE_SCREEN_BF16X3)
-    return d <= 32 && (size_t)(kpad32(k) / 32) * (4096 + 128) <= LDS_BUDGET &&
-                   !AB_NO_W32
+    return d <= 32 && (size_t)(kpad32(k) / 32) * (4096 + 128) <= LDS_BUDGET
                ? IMG_SPLIT
                : IMG_NONE;
   return IMG_NONE;
@@ -4581,7 +3761,8 @@ int dkm_add_f64_dd(double *hi, double *lo, const double *x, int64_t n,
 // (variants.sh / variants_b2.sh builds only): the library reports them,
 // and tests/test_isa_guard.py requires 0 of the in-tree product build.
 int dkm_build_flags(void) {
-  return tu_flags_util() | tu_flags_dense() | tu_flags_b2() |
+  return tu_flags_util() | tu_flags_dense() | tu_flags_recheck() |
+         tu_flags_b2() |
          tu_flags_sorted() | tu_flags_cand() | tu_flags_sparse() |
          tu_flags_gemm() | tu_flags_sums() | tu_flags_neighbors();
 }
@@ -4591,12 +3772,7 @@ int dkm_build_flags(void) {
 // Code-object preload (dkm_preload): the runtime loads this file's kernels
 // on first use of any of them; an attribute query here does it up front.
 namespace dkm {
-#if DKM_AB_B1_PROBE || defined(DKM_DBG_NOCOMPUTE) || defined(DKM_DBG_NOLOAD)
-#define DKM_DENSE_PROBE 1
-#else
-#define DKM_DENSE_PROBE 0
-#endif
-DKM_TU_FLAGS(dense, DKM_DENSE_PROBE)
+DKM_TU_FLAGS(dense, 0)
 __global__ void k_tu_dense() {}
 int preload_dense() {
   hipFuncAttributes a;

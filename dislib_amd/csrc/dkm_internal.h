@@ -22,6 +22,7 @@ void set_error(const std::string &msg);
 int fail(int code, const std::string &msg);
 // Per-file code-object preload (each .hip file's kernels load on first use).
 int preload_dense();
+int preload_recheck();
 int preload_b2();
 int preload_sorted();
 int preload_cand();
@@ -45,6 +46,7 @@ int check_launch(const char *what);
   }
 int tu_flags_util();
 int tu_flags_dense();
+int tu_flags_recheck();
 int tu_flags_b2();
 int tu_flags_sorted();
 int tu_flags_cand();

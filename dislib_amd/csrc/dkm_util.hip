@@ -636,9 +636,9 @@ const char *dkm_last_error(void) { return g_err.c_str(); }
 int dkm_preload(void) {
   hipFuncAttributes a;
   int bad = hipFuncGetAttributes(&a, (const void *)k_prepare) != hipSuccess;
-  bad += preload_dense() + preload_b2() + preload_sorted() + preload_cand() +
-         preload_sparse() + preload_gemm() + preload_sums() +
-         preload_neighbors();
+  bad += preload_dense() + preload_recheck() + preload_b2() +
+         preload_sorted() + preload_cand() + preload_sparse() +
+         preload_gemm() + preload_sums() + preload_neighbors();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

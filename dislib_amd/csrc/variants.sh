@@ -1,12 +1,10 @@
 #!/bin/bash
 # Build A/B variants of libdkm.so (screen-kernel compile-time knobs) next to
 # the default library: ../libdkm_<name>.so.  usage: bash variants.sh name "DEFS" ...
-# A/B switches are compile-time only (-DDKM_AB_NO_W32=1, -DDKM_AB_DELTA_POST=1,
-# -DDKM_AB_NO_POST=1, -DDKM_AB_NO_LIST=1, -DDKM_AB_CSR_OLD=1,
-# -DDKM_AB_BLOCKS_PER_CU=n, -DDKM_AB_VERBOSE, -DDKM_AB_SBB=n (k_screen_b1
-# block size), -DDKM_AB_B1_PREFETCH=1 (k_screen_b1 next-tile prefetch)): the
-# product build reads no
-# environment variable.  Every object is compiled with -DDKM_AB_VARIANT=1,
+# A/B switches are compile-time only (-DDKM_AB_BLOCKS_PER_CU=n and
+# -DDKM_AB_VERBOSE in resident_blocks, dkm_dense.hip; the DKM_AB_* knobs of
+# dkm_b2.hip and dkm_sorted.hip): the product build reads no environment
+# variable for them.  Every object is compiled with -DDKM_AB_VARIANT=1,
 # so dkm_build_flags() of such a library is non-zero (bench.py records it,
 # the tests refuse it).
 set -e

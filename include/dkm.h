@@ -416,8 +416,8 @@ int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
 
 /* Build flags of this library: 0 for a product build.  DKM_BUILD_TIMING_ONLY
  * when an object was compiled with an A/B timing probe that invalidates
- * results (DKM_AB_B1_PROBE, DKM_AB_B2_PROBE, DKM_AB_SORTED_BSCALE != 1,
- * DKM_AB_SORTED_DBG, DKM_DBG_NOCOMPUTE, ...); DKM_BUILD_AB_VARIANT when any
+ * results (DKM_AB_B2_PROBE, DKM_AB_SORTED_BSCALE != 1, DKM_AB_SORTED_DBG);
+ * DKM_BUILD_AB_VARIANT when any
  * object comes from an A/B variant build (csrc/variants*.sh).  bench.py
  * records a non-zero value in its line, and tests/test_isa_guard.py checks
  * that the in-tree library reports 0. */

@@ -55,7 +55,7 @@ SOURCES = _sources()
 
 def test_sources_come_from_the_makefile():
     for s in ("dkm_sorted.hip", "dkm_cand.hip", "dkm_b2.hip", "dkm_dense.hip",
-              "dkm_gemm.hip", "dkm_sparse.hip"):
+              "dkm_gemm.hip", "dkm_sparse.hip", "dkm_recheck.hip"):
         assert s in SOURCES
 
 
