@@ -459,6 +459,81 @@ def label_sums(dd, ws, labels, acc, k):
                   ws.p, ws.nbytes, ptr(acc), stream_ptr()), "dkm_label_sums")
 
 
+class OrderedSums:
+    """Buffers of a sums="reference" fit (dkm_ordered_sums_* and
+    dkm_merge_tree): the grouping workspace, the Subset offsets on the
+    device, the partials of ALL ranks' Subsets (``n_total`` x k (d + 1) fp64;
+    this rank fills the ``dd``'s Subsets from slot ``first``) and the merge
+    schedule with its scratch.  Raises ValueError when the partials and the
+    scratch would leave less than 4 GiB of HBM free."""
+
+    def __init__(self, dd, k, first, n_total, schedule, n_ops, n_slots):
+        t = torch()
+        so = _lib.lib()
+        self.k, self.len = int(k), int(k) * (dd.d + 1)
+        self.n_local, self.first = len(dd.sizes), int(first)
+        self.n_total, self.n_ops = int(n_total), int(n_ops)
+        nb = (self.n_total + int(n_slots)) * self.len * 8
+        free = t.cuda.mem_get_info(dd.device)[0]
+        if nb + _IMAGE_HEADROOM > free:
+            raise ValueError(
+                "sums='reference' keeps one partial [sums | counts] per "
+                "Subset: %d Subsets x k (d + 1) = %d values need %.2f GiB "
+                "of HBM, and %.2f GiB are free (4 GiB stay free); use "
+                "larger Subsets" % (self.n_total, self.len, nb / 2.0 ** 30,
+                                    free / 2.0 ** 30))
+        self.partials = _alloc("partials", self.n_total * self.len * 8,
+                               lambda: t.zeros(self.n_total * self.len,
+                                               dtype=t.float64,
+                                               device=dd.device))
+        self.scratch = t.empty(max(1, int(n_slots)) * self.len,
+                               dtype=t.float64, device=dd.device)
+        self.schedule = t.from_numpy(np.ascontiguousarray(
+            schedule, dtype=np.int32)).to(dd.device) if n_ops else None
+        self.offsets = t.from_numpy(np.ascontiguousarray(
+            dd.offsets, dtype=np.int64)).to(dd.device)
+        self.ws = None
+        if self.n_local:
+            nws = int(so.dkm_ordered_workspace_bytes(dd.n, self.n_local,
+                                                     self.k, dd.d))
+            if nws == 0:
+                raise ValueError(
+                    "sums='reference' takes n < 2**31 - 1 rows per rank and "
+                    "k <= 8191, got n = %d, k = %d" % (dd.n, self.k))
+            self.ws = _alloc("ordered", nws, lambda: t.empty(
+                nws, dtype=t.uint8, device=dd.device))
+
+    def group_order(self, n):
+        """The row indices grouped stably by (Subset, label) that the last
+        :func:`ordered_sums` left in the workspace (int32 view)."""
+        return self.ws[:4 * n].view(torch().int32)
+
+
+def ordered_sums(dd, labels, osum):
+    """This rank's slots of ``osum.partials`` <- the per-Subset [sums |
+    counts] of X by labels in the reference's order (dkm_ordered_sums_*)."""
+    if osum.n_local == 0:
+        return
+    so = _lib.lib()
+    fn = so.dkm_ordered_sums_f32 if dd.dtype == np.float32 else \
+        so.dkm_ordered_sums_f64
+    own = osum.partials[osum.first * osum.len:]
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(labels), osum.k, ptr(osum.offsets), osum.n_local,
+                  ptr(osum.ws), osum.ws.numel(), ptr(own), stream_ptr()),
+               "dkm_ordered_sums")
+
+
+def merge_tree(osum, acc, f32):
+    """acc <- the arity tree's root over ``osum.partials``
+    (dkm_merge_tree); fp32 samples' sums fold in fp32."""
+    so = _lib.lib()
+    _lib.check(so.dkm_merge_tree(
+        ptr(osum.partials), osum.n_total, osum.len, ptr(osum.schedule),
+        osum.n_ops, osum.k * (osum.len // osum.k - 1) if f32 else 0,
+        ptr(osum.scratch), ptr(acc), stream_ptr()), "dkm_merge_tree")
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

@@ -192,3 +192,66 @@ def agree(flag_value):
     t = torch.tensor([flag_value, -flag_value], dtype=torch.int64, device=dev)
     d.all_reduce(t, op=d.ReduceOp.MAX)
     return int(t[0]) == flag_value and int(-t[1]) == flag_value
+
+
+# ---------------------------------------------------------------------------
+# sums="reference": the reference's arity tree, kept (not replaced)
+# ---------------------------------------------------------------------------
+def merge_schedule(n_partials, arity):
+    """The reduction loop of ``_recompute_centers`` (base.py:137-141) over
+    ``n_partials`` per-Subset partials, flattened for ``dkm_merge_tree``:
+    ``(schedule, n_ops, n_slots)``.
+
+    The loop keeps a queue of the partials in Subset order; while more than
+    one remains it pops the first ``arity``, folds them left to right
+    (``_merge``, base.py:184-191) and appends the result at the tail.
+    ``schedule`` is an int32 array of ``n_ops`` ops ``[dst, count, src_0 ..
+    src_{count-1}]``: a source below ``n_partials`` is that partial, any
+    other is slot ``src - n_partials`` of a scratch of ``n_slots`` buffers
+    (a slot is reused once its value has been folded); ``dst`` is a slot, or
+    -1 for the root (the last op).  One partial needs no op.  With ``arity <
+    2`` and more than one partial the reference's loop never ends: that is
+    a ValueError here."""
+    import collections
+
+    import numpy as np
+    n = int(n_partials)
+    if n < 1:
+        raise ValueError("merge_schedule: no partials")
+    if n > 1 and arity < 2:
+        raise ValueError("arity must be >= 2 to merge %d Subsets (the "
+                         "reference's reduction never ends), got %r"
+                         % (n, arity))
+    queue = collections.deque(range(n))
+    free, n_slots, out, n_ops = [], 0, [], 0
+    while len(queue) > 1:
+        group = [queue.popleft() for _ in range(min(int(arity), len(queue)))]
+        free.extend(g - n for g in group if g >= n)
+        if queue:
+            if free:
+                dst = free.pop()
+            else:
+                dst, n_slots = n_slots, n_slots + 1
+            queue.append(n + dst)
+        else:
+            dst = -1
+        out.extend([dst, len(group)] + group)
+        n_ops += 1
+    return np.asarray(out, dtype=np.int32), n_ops, n_slots
+
+
+def subset_slots(n_local, device=None):
+    """(first global Subset index of this rank, Subsets of all ranks): the
+    ranks own contiguous blocks of Subsets in rank order, so one all-reduced
+    vector of the per-rank Subset counts places every rank's partials."""
+    d = _dist()
+    if d is None or d.get_world_size() == 1:
+        return 0, int(n_local)
+    import torch
+    rank, size = d.get_rank(), d.get_world_size()
+    dev = device if d.get_backend() == "nccl" else "cpu"
+    t = torch.zeros(size, dtype=torch.float64, device=dev)
+    t[rank] = float(n_local)
+    allreduce_sum_(t)
+    counts = [int(v) for v in t.tolist()]
+    return sum(counts[:rank]), sum(counts)

@@ -18,13 +18,27 @@ Same constructor, attributes and semantics as the reference:
   update); ``predict`` labels from ``centers``.
 
 Differences (documented in DESIGN.md): the per-Subset tasks become one fused
-kernel launch over the device-resident data, and the partial sums are
-accumulated in a different order than the reference's sequential
-Subset-then-arity-tree order, so centres agree to ~1e-15 relative instead of
-bit-for-bit; ``arity`` is kept but has no effect on the GPU (no reduction
-tree).  Extra keyword-only arguments select the assignment arithmetic
-(``mode``: "auto" | "exact" | "screen32" | "bf16x3" | "bf16", identical
-labels) and the device.
+kernel launch over the device-resident data, and by default (``sums="fast"``)
+the partial sums are accumulated in a different order than the reference's
+sequential Subset-then-arity-tree order, so centres agree to ~1e-15 relative
+instead of bit-for-bit, and ``arity`` has no effect (no reduction tree).
+Extra keyword-only arguments select the assignment arithmetic (``mode``:
+"auto" | "exact" | "screen32" | "bf16x3" | "bf16", identical labels), the
+summation order (``sums``) and the device.
+
+``sums="reference"`` reproduces the reference's sums: one sequential chain
+per (Subset, cluster, column) in row order (dkm_ordered_sums_*), merged by
+the ``arity`` tree (dkm_merge_tree), for dense fp64, fp32 (a true fp32
+chain and fp32 merges) and integer samples (uploaded as fp64: exact while
+every |sum| < 2**53).  Centres are then bit-identical to dislib's, from run
+to run and for any number of ranks.  Its cost: every iteration reads X once
+more and recomputes the sums in full (no delta sums, no label-sorted image,
+no bounds), the parallelism of the sums is Subsets x k x d chains (a Dataset
+of one Subset is slow by definition of the order), and one partial of
+k (d + 1) fp64 per Subset of the whole Dataset stays in HBM (a ValueError
+when that would leave less than 4 GiB free).  CSR data is not supported in
+this mode (NotImplementedError); ``arity < 2`` with more than one Subset,
+with which the reference never terminates, is a ValueError.
 """
 import os
 
@@ -36,6 +50,7 @@ from .. import _lib, _shard
 _MODES = {"auto": _lib.MODE_AUTO, "exact": _lib.MODE_EXACT,
           "screen32": _lib.MODE_SCREEN32, "bf16x3": _lib.MODE_BF16X3,
           "bf16": _lib.MODE_BF16}
+_SUMS = ("fast", "reference")
 
 
 def _init_centers(n_features, sparse, n_clusters, random_state):
@@ -51,7 +66,9 @@ class KMeans:
     """Perform K-means clustering (Lloyd) on MI355X.
 
     Parameters match ``dislib.cluster.KMeans``; ``mode`` and ``device`` are
-    keyword-only extensions.  Under ``torch.distributed`` with more than one
+    keyword-only extensions, ``sums`` too ("fast": the default order;
+    "reference": the reference's order, bit-identical centres -- see the
+    module docstring).  Under ``torch.distributed`` with more than one
     rank, each rank passes its own shard Dataset (see
     :func:`dislib_amd.shard_dataset`) and the per-iteration [sums | counts]
     are all-reduced (RCCL).
@@ -59,7 +76,7 @@ class KMeans:
 
     def __init__(self, n_clusters=8, max_iter=10, tol=1e-4, arity=50,
                  random_state=None, verbose=False, *, mode="auto",
-                 device=None):
+                 device=None, sums="fast"):
         self._n_clusters = n_clusters
         self._max_iter = max_iter
         self._tol = tol
@@ -71,6 +88,9 @@ class KMeans:
         if mode not in _MODES:
             raise ValueError("mode must be one of %s" % sorted(_MODES))
         self._mode = mode
+        if sums not in _SUMS:
+            raise ValueError("sums must be one of %s" % sorted(_SUMS))
+        self._sums = sums
         self._device = device
         self._rechecked = 0
 
@@ -119,11 +139,16 @@ class KMeans:
                             "(np.random.seed, as in the reference)")
         _lib.lib()                          # no GPU / no libdkm: raise here
         sparse = dataset.sparse
+        if sparse and self._sums == "reference":
+            raise NotImplementedError(
+                "sums='reference' takes dense samples: the reference's sparse "
+                "partials are scipy CSR sums with their own structure rules")
         centers = _init_centers(dataset.n_features, sparse, self._n_clusters,
                                 self._random_state)
         state = _Lloyd(dataset, centers.toarray() if sparse else centers,
                        self._tol, set_labels, self._mode, self._device,
-                       broadcast_init=self._random_state is None)
+                       broadcast_init=self._random_state is None,
+                       sums=self._sums, arity=self._arity)
         iteration = 0
         while True:
             conv = state.step()
@@ -193,10 +218,17 @@ class _Lloyd:
     (dkm_assign_delta*: only samples whose label changed move their row
     between clusters; dense and CSR) and recomputes ``state`` from scratch
     (dkm_partial_sum) on the first and every REFRESH-th iteration, which
-    bounds the rounding drift of the running sums."""
+    bounds the rounding drift of the running sums.
+
+    With ``sums="reference"`` every iteration is: prepare -> labels
+    (dkm_predict_*) -> per-Subset ordered sums (dkm_ordered_sums_*) ->
+    all-reduce of the zero-filled partials of all ranks' Subsets (adding +0.0
+    is exact and no partial holds -0.0: every rank gets the single-process
+    bits) -> the ``arity`` tree (dkm_merge_tree) -> centre update.  No delta
+    sums, sorted image or bounds: any of them would change the order."""
 
     def __init__(self, dataset, centers, tol, set_labels, mode="auto",
-                 device=None, broadcast_init=False):
+                 device=None, broadcast_init=False, sums="fast", arity=50):
         from .._device import Workspace, on, torch
         t = torch()
         self.dataset = dataset
@@ -254,6 +286,17 @@ class _Lloyd:
                          bounds_ok(dd, k, self.mode, self.ws))
         self.bounds = None        # (2, n) fp32 once allocated
         self.bounds_valid = False  # they hold for self.labels
+        self.osum = None
+        if sums == "reference":
+            if self.sparse:
+                raise NotImplementedError("sums='reference': dense only")
+            from .._device import OrderedSums
+            self.sorting = self.bounding = False
+            first, total = _shard.subset_slots(len(dd.sizes), dd.device)
+            sched, n_ops, n_slots = _shard.merge_schedule(total, arity)
+            with self._on():
+                self.osum = OrderedSums(dd, k, first, total, sched, n_ops,
+                                        n_slots)
 
     def prepare(self):
         """Per-iteration centre data + zeroed accumulator."""
@@ -262,6 +305,8 @@ class _Lloyd:
             prepare(self.C, self.ws, self.acc, csr=self.sparse)
 
     def _full(self):
+        if self.osum is not None:
+            return True
         # iteration 1 recomputes too: its labels are the first against
         # centres that are means of samples, and most samples move (a delta
         # pass would add and subtract most rows: 2x a full pass at C3)
@@ -273,6 +318,8 @@ class _Lloyd:
         """
         from .._device import (assign_delta, label_sums, partial_sum,
                                predict, sorted_image)
+        if self.osum is not None:
+            return self._partial_reference()
         if self.dd.n == 0:
             return
         mode = self.mode
@@ -341,6 +388,22 @@ class _Lloyd:
                              mode, image=image)
                 self.bounds_valid = False
 
+    def _partial_reference(self):
+        """Labels only, then this rank's per-Subset partials in the
+        reference's order; the all-reduce and the tree follow in
+        reduce_update."""
+        from .._device import ordered_sums, predict
+        mode = self.mode
+        if mode == _lib.MODE_AUTO and self.it == 0:
+            mode = _lib.MODE_BF16X3   # crowded initial centres: see partial()
+        with self._on():
+            if _shard.active():
+                self.osum.partials.zero_()   # the other ranks' slots add +0.0
+            if self.dd.n:
+                predict(self.dd, self.C, self.ws, self.labels[:self.dd.n],
+                        mode)
+            ordered_sums(self.dd, self.labels, self.osum)
+
     def _bounds_image(self):
         """The built split image of a delta iteration that keeps bounds (they
         are allocated here, at the first such iteration), else None."""
@@ -364,7 +427,13 @@ class _Lloyd:
     def reduce_update(self):
         from .._device import add_dd_, update
         with self._on():
-            _shard.allreduce_sum_(self.acc)
+            if self.osum is not None:
+                from .._device import merge_tree
+                _shard.allreduce_sum_(self.osum.partials)
+                merge_tree(self.osum, self.acc,
+                           self.sums_mode == _lib.SUMS_F32)
+            else:
+                _shard.allreduce_sum_(self.acc)
             self._was_full = self._full()
             if self._was_full:
                 self.state.copy_(self.acc)

@@ -3764,7 +3764,8 @@ int dkm_build_flags(void) {
   return tu_flags_util() | tu_flags_dense() | tu_flags_recheck() |
          tu_flags_b2() |
          tu_flags_sorted() | tu_flags_cand() | tu_flags_sparse() |
-         tu_flags_gemm() | tu_flags_sums() | tu_flags_neighbors();
+         tu_flags_gemm() | tu_flags_sums() | tu_flags_neighbors() |
+         tu_flags_ordered();
 }
 
 }  // extern "C"

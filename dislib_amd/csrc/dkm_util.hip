@@ -638,7 +638,8 @@ int dkm_preload(void) {
   int bad = hipFuncGetAttributes(&a, (const void *)k_prepare) != hipSuccess;
   bad += preload_dense() + preload_recheck() + preload_b2() +
          preload_sorted() + preload_cand() + preload_sparse() +
-         preload_gemm() + preload_sums() + preload_neighbors();
+         preload_gemm() + preload_sums() + preload_neighbors() +
+         preload_ordered();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 4
+#define DKM_ABI_VERSION 5
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -293,6 +293,58 @@ int dkm_label_sums_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
 int dkm_label_sums_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                        const int32_t *labels, int64_t k, const void *ws,
                        size_t ws_bytes, double *acc, void *stream);
+
+/* -----------------------------------------------------------------------
+ * The reference's own summation order (KMeans sums="reference"): centres
+ * bit-identical to dislib's, from run to run and for any number of ranks.
+ * No floating-point atomic; no result depends on a grid or block size.
+ *
+ * dkm_ordered_sums_*: the sums half of `_partial_sum` (base.py:166-181:
+ * `partials[label][0] += sample`, `partials[label][1] += 1`) for every
+ * Subset at once.  subset_off (device int64[n_subsets + 1], ascending,
+ * subset_off[0] = 0, subset_off[n_subsets] = n) cuts the rows of X into
+ * Subsets.  For Subset s, cluster c and column j the rows of s with label c
+ * are added in ascending row order in ONE sequential chain that starts from
+ * +0.0 (the reference's integer 0 placeholder adds like +0.0, so no partial
+ * holds -0.0): an fp64 chain for fp64 rows; for fp32 rows a true fp32 chain
+ * (every add rounded to fp32, subnormals kept), stored widened, which is
+ * exact.  Integer samples uploaded as fp64 are exact while |sum| < 2^53.
+ * partials (n_subsets x k (d + 1) fp64, every element written): Subset s at
+ * partials + s k (d + 1), laid out [sums k x d | counts k] like `acc`; the
+ * counts are integers.  Labels outside [0, k) are skipped, as in
+ * dkm_label_sums_*.  ws: dkm_ordered_workspace_bytes(n, n_subsets, k, d)
+ * bytes (0: shape refused -- n < 2^31 - 1, k <= 8191); after the call its
+ * first n int32 hold the row indices grouped stably by (Subset, label)
+ * (labels outside [0, k) last in their Subset).  Cost: one more read of X,
+ * and the parallelism is n_subsets x k x d chains -- one Subset is slow by
+ * definition of the order.                                                */
+size_t dkm_ordered_workspace_bytes(int64_t n, int64_t n_subsets, int64_t k,
+                                   int64_t d);
+int dkm_ordered_sums_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                         const int32_t *labels, int64_t k,
+                         const int64_t *subset_off, int64_t n_subsets,
+                         void *ws, size_t ws_bytes, double *partials,
+                         void *stream);
+int dkm_ordered_sums_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                         const int32_t *labels, int64_t k,
+                         const int64_t *subset_off, int64_t n_subsets,
+                         void *ws, size_t ws_bytes, double *partials,
+                         void *stream);
+/* The reduction loop of `_recompute_centers` with `_merge` (base.py:137-141,
+ * 184-191): acc[len] <- the root of the arity tree over the n_partials
+ * buffers of `len` fp64 each; one thread per element walks the tree.
+ * `schedule` (device int32) is the tree, flattened on the host: n_ops ops
+ * [dst, count, src_0 .. src_{count-1}], each folding its sources left to
+ * right (acc = src_0; acc += src_1; ...).  A source i < n_partials is
+ * partials[i], else slot i - n_partials of `scratch` (slots of `len` fp64);
+ * dst is a scratch slot, or -1 for `acc` (the last op).  n_ops = 0 (one
+ * partial): acc <- partials[0].  sums_f32: the leading elements of every
+ * buffer that fold in fp32 (k d for fp32 samples -- the reference's fp32
+ * sums merge in fp32 --, 0 otherwise); the rest (the integer counts) fold
+ * in fp64.  The schedule is trusted: its indices are not checked.          */
+int dkm_merge_tree(const double *partials, int64_t n_partials, int64_t len,
+                   const int32_t *schedule, int64_t n_ops, int64_t sums_f32,
+                   double *scratch, double *acc, void *stream);
 
 /* y[i] += x[i] (device, fp64): acc_new = acc_old + delta.                  */
 int dkm_add_f64(double *y, const double *x, int64_t n, void *stream);
