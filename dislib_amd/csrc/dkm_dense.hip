@@ -3510,6 +3510,14 @@ int dkm_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                        mode, stream, "dkm_predict_f32");
 }
 
+// The shapes whose delta calls keep per-row bounds: bounds_shape, and sums
+// that fit LDS beside the w32 fragments -- plan_screen's `post` calls (sums
+// from the labels, the old labels copied into the label scratch) do not list
+// their moved rows, and the bounds call rests on that list.
+int dkm_bounds_ok(int64_t k, int64_t d) {
+  return bounds_shape(k, d) && sums_fit_lds(k, d) ? 1 : 0;
+}
+
 int dkm_x_image_kind(int64_t k, int64_t d, int mode) {
   if (k <= 0 || d <= 0 || k > INT32_MAX || d > INT32_MAX) return IMG_NONE;
   mode &= DKM_MODE_MASK;

@@ -755,8 +755,6 @@ int dkm_bounds_counters(const void *ws, int64_t *out, void *stream) {
   return 0;
 }
 
-int dkm_bounds_ok(int64_t k, int64_t d) { return bounds_shape(k, d) ? 1 : 0; }
-
 int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
                      void *stream) {
   if (!ws || !out) return fail(DKM_E_ARG, "screen_lists: NULL");

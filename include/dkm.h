@@ -258,7 +258,8 @@ int dkm_assign_delta_img_f32(const float *X, const void *image, int image_kind,
  *     screen over all rows runs instead; the choice is made on the device.
  *     DKM_BOUNDS_INIT calls run no bounds pass and are not counted by
  *     dkm_bounds_counters.
- * Shapes: dkm_bounds_ok(k, d) (d <= 32, 2 <= k <= 256; any ldx), mode
+ * Shapes: dkm_bounds_ok(k, d) (d <= 32, 2 <= k <= 256 and [sums | counts]
+ * that fit LDS beside the centres: k <= 192 at d = 32; any ldx), mode
  * AUTO or SCREEN_BF16X3 without flags, a built DKM_IMAGE_SPLIT image, a
  * workspace with n label slots (dkm_workspace_bytes(k, d, n_queue >= n));
  * anything else is refused with DKM_E_ARG.  Replaces the same reference
