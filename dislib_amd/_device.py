@@ -397,6 +397,16 @@ def bounds_counters(ws):
     return tuple(int(x) for x in out)
 
 
+def bounds_settled(ws):
+    """Rows the exact re-check's fp32 stage gave bounds to, over the
+    workspace's life (dkm_bounds_settled)."""
+    so = _lib.lib()
+    out = ctypes.c_int64(0)
+    _lib.check(so.dkm_bounds_settled(ws.p, ctypes.byref(out), stream_ptr()),
+               "dkm_bounds_settled")
+    return int(out.value)
+
+
 def sorted_image_ok(dd, k):
     """Does the fit's auto mode on (k, d) run the single-product screen that
     takes a label-sorted image (dkm_x_image_sorted_ok)?"""

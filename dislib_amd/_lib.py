@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DKM_LIB", os.path.join(_HERE, "libdkm.so"))
 
 # constants mirrored from include/dkm.h
-ABI_VERSION = 5
+ABI_VERSION = 6
 MODE_AUTO, MODE_EXACT, MODE_SCREEN32, MODE_BF16X3, MODE_BF16 = 0, 1, 2, 3, 4
 MODE_MASK, MODE_NOHINT, MODE_B1, MODE_TRANSLATE = 0xff, 0x100, 0x200, 0x400
 IMAGE_NONE, IMAGE_SINGLE, IMAGE_SPLIT, IMAGE_SORTED, IMAGE_GEMM = 0, 1, 2, 3, 4
@@ -72,6 +72,7 @@ SIGNATURES = {
                                            _i64, _p, _i64, _p, _sz, _p, _p,
                                            _i32, _p, _p, _i32, _p]),
     "dkm_bounds_counters": (_i32, [_p, ctypes.POINTER(_i64), _p]),
+    "dkm_bounds_settled": (_i32, [_p, ctypes.POINTER(_i64), _p]),
     "dkm_label_sums_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,
                                   _p, _p]),
     "dkm_label_sums_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,

@@ -478,6 +478,12 @@ class _Lloyd:
         with self._on():
             return bounds_counters(self.ws)
 
+    def bounds_settled(self):
+        """Rows the exact re-check gave bounds to so far."""
+        from .._device import bounds_settled
+        with self._on():
+            return bounds_settled(self.ws)
+
     def rechecked(self):
         from .._device import rechecked
         with self._on():

@@ -147,15 +147,24 @@ inline int acc_mode(int acc_kind, bool lds_fits) {
   return AM_ON | (acc_kind == 2 ? AM_DELTA : 0) | (lds_fits ? AM_INLDS : 0);
 }
 
-// dkm_recheck.hip (the <double> / <float> forms are instantiated there)
+// A bounds call's (ub, lb) arrays as the re-checks take
+// them: a row their fp32 stage decides gets its bounds there.
+struct RcBnd {
+  float *ub, *lb;
+};
+
+// dkm_recheck.hip (the <double> / <float> forms are instantiated there).
+// bnd: a bounds call (d <= 32, not wave_all); null: no bounds are written.
 bool list_ok(int64_t k, int64_t d);
 template <class TX>
 int launch_list(const TX *X, int d, int64_t ldx, int k, const WsView &v,
                 int32_t *lab_out, double *acc, int acc_kind, bool vec,
-                int64_t base, int nseg, hipStream_t s, bool wave_all = false);
+                int64_t base, int nseg, hipStream_t s, bool wave_all = false,
+                const RcBnd *bnd = nullptr);
 template <class TX>
 int launch_recheck(const TX *X, int64_t end, int d, int64_t ldx, int k,
                    const WsView &v, int32_t *lab_out, double *acc,
-                   int acc_kind, bool vec, int64_t base, hipStream_t s);
+                   int acc_kind, bool vec, int64_t base, hipStream_t s,
+                   const RcBnd *bnd = nullptr);
 
 }  // namespace dkm

@@ -789,7 +789,8 @@ __device__ __forceinline__ void wave_sync_w() {
 // every other centre, from its own score, the least score of the others
 // (a running minimum of the threshold pass's per-block minima; p's slot is
 // poisoned, so it leaves p out) and the screen's bound B; a row left to the
-// re-check gets (+inf, 0).  With IMG the pass is the image screen over all
+// re-check gets (+inf, 0) here, and the re-check's fp32 stage overwrites it
+// when it decides the row (resolve_lane<..., BND>, dkm_recheck.hip).  With IMG the pass is the image screen over all
 // rows; without, its list form: the wave's 32 rows are list[32 t + r] (the
 // rows the bounds pass left active), read and converted from X, and every
 // per-row result goes back to that row.  In an update call (bnd.upd) the
@@ -2519,6 +2520,14 @@ static double bounds_list_frac() {
   return end == e ? BOUNDS_LIST_FRAC : f;
 }
 
+// DKM_BOUNDS_SETTLE=0 in the environment (read at every call, for A/B runs):
+// the re-checks of a bounds call write no bounds, and every row they take
+// keeps the screen's (+inf, 0)
+static bool bounds_settle() {
+  const char *e = getenv("DKM_BOUNDS_SETTLE");
+  return !(e && e[0] == '0' && !e[1]);
+}
+
 template <class TX>
 static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
                              int k, const WsView &v, int32_t *lab_out,
@@ -3134,12 +3143,17 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
     if (p.rescreen &&
         (r = rescreen_list<TX>(X, d, ldx, C, k, v, lab_out, base, nseg, s)))
       return r;
+    // a bounds call: the re-checks' fp32 stage writes the bounds of the rows
+    // it decides (the screen left them at (+inf, 0))
+    const RcBnd rcb{o.bnds ? o.bnds->ub : nullptr,
+                    o.bnds ? o.bnds->lb : nullptr};
+    const RcBnd *rb = (o.bnds && bounds_settle()) ? &rcb : nullptr;
     if ((p.use_list || b1) &&
         (r = launch_list<TX>(X, d, ldx, k, v, lab_out, acc, p.skind, p.vec,
-                             base, nseg, s, o.sub)))
+                             base, nseg, s, o.sub, rb)))
       return r;
     if ((r = launch_recheck<TX>(X, end, d, ldx, k, v, lab_out, acc, p.skind,
-                                p.vec, base, s)))
+                                p.vec, base, s, rb)))
       return r;
     // the sorted image's label copy: the rows the re-checks decided (and,
     // premoved, the list of rows that moved)

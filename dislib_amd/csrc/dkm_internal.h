@@ -91,8 +91,10 @@ struct WsHeader {
   uint32_t pad4;
   // ... and the counters of dkm_bounds_counters
   uint64_t bnd_calls, bnd_active, bnd_skipped, bnd_list_calls;
+  // rows the exact re-check's fp32 stage gave bounds to (dkm_bounds_settled)
+  uint64_t bnd_settled;
 };
-constexpr uint64_t WS_MAGIC = 0x444b4d5753303036ull;  // "DKMWS006"
+constexpr uint64_t WS_MAGIC = 0x444b4d5753303037ull;  // "DKMWS007"
 constexpr size_t WS_HDR = 256;
 static_assert(sizeof(WsHeader) <= WS_HDR, "the header fits WS_HDR");
 

@@ -27,11 +27,42 @@ __device__ __forceinline__ void wave_lds_sync() {
 // the row between the accumulators as amode says (prev = previous label).
 // STAGE1_ONLY: return false (writing nothing) when stage 1 cannot decide,
 // so the caller can batch the rare stage-2 samples into full waves.
-template <int MAXD, bool VEC, class TX, bool STAGE1_ONLY = false>
+// BND (a bounds call): a row stage 1 decides also gets its
+// (ub, lb) under this call's centres, from the two best fp32 scores over all
+// k centres (settle_bounds below), and is counted in nset; a row that goes on
+// to stage 2 is not written: it keeps the screen's (+inf, 0).
+template <bool UP>
+__device__ __forceinline__ float f32_outward(double v) {  // v >= 0
+  float f = (float)v;
+  if (UP) {
+    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
+  } else {
+    if ((double)f > v) f = __uint_as_float(__float_as_uint(f) - 1u);
+  }
+  return f;
+}
+// Every fp32 score is within B / 2 of |c|^2 - 2 x.c under the fp64 centres
+// (screen_bound<P_F32> is twice the rigorous bound, the rounding of the
+// centres to c32 / cn32 included: DESIGN.md 3.14), and xx, the fp32 fma chain
+// of d <= 32 squares of fl32(x), within 35 x 2^-24 < 2^-18.8 of |x|^2.  So
+// u^2 = xx (1 + 2^-18) + b1 + B and l^2 = xx (1 - 2^-18) + b2 - B bound the
+// squared distances with B / 2 + 2^-19.3 xx to spare; they and the roots are
+// evaluated in fp64 (roundings of 2^-53: nothing against that spare), and
+// the roots are rounded outwards to fp32 once.
+__device__ __forceinline__ void settle_bounds(float xx, float b1, float b2,
+                                              float B, float *ub, float *lb) {
+  const double u2 = fma((double)xx, 1.0 + 0x1.0p-18, (double)b1 + (double)B);
+  const double l2 = fma((double)xx, 1.0 - 0x1.0p-18, (double)b2 - (double)B);
+  *ub = f32_outward<true>(sqrt(fmax(u2, 0.0)));
+  *lb = f32_outward<false>(sqrt(fmax(l2, 0.0)));
+}
+template <int MAXD, bool VEC, class TX, bool STAGE1_ONLY = false,
+          bool BND = false>
 __device__ __forceinline__ bool resolve_lane(
     const TX *__restrict__ X, int64_t ldx, int d, int k, int64_t i, int prev,
     const float *cl, const float *cnl, int dp, float cm, const double *ct64,
-    int32_t *lab_out, int amode, const AccTarget &at) {
+    int32_t *lab_out, int amode, const AccTarget &at, RcBnd rb = RcBnd{},
+    unsigned *nset = nullptr) {
   const TX *xr = X + i * ldx;
   float xf[MAXD];
   float xx = 0.f;
@@ -116,6 +147,13 @@ __device__ __forceinline__ bool resolve_lane(
         bi = jc;
       }
     }
+  } else if constexpr (BND) {
+    // decided by stage 1: the label is i1 and b2 the least score of every
+    // other centre (the scan was over all k)
+    if (b2 < 1e30f) {
+      settle_bounds(xx, b1, b2, B, rb.ub + i, rb.lb + i);
+      *nset += 1u;
+    }
   }
   lab_out[i] = bi;
   if (!(amode & AM_ON)) return true;
@@ -175,6 +213,17 @@ __device__ __forceinline__ void recheck_finish_count(
   __syncthreads();
   if (threadIdx.x == 0 && *blk_count)
     atomicAdd((unsigned long long *)&v.hdr->rechecked_total, *blk_count);
+}
+
+// BND kernels: the rows that got bounds, per block and then in the header
+__device__ __forceinline__ void recheck_finish_settled(
+    unsigned nset, unsigned long long *blk_settled, const WsView &v) {
+  if (nset)
+    __hip_atomic_fetch_add(blk_settled, (unsigned long long)nset,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  if (threadIdx.x == 0 && *blk_settled)
+    atomicAdd((unsigned long long *)&v.hdr->bnd_settled, *blk_settled);
 }
 
 // resolve_lane's two stages for ONE sample i with the whole wave: lanes
@@ -271,177 +320,14 @@ static size_t recheck_lane_lds(int64_t, int64_t) {
   return (size_t)(BLOCK / 64) * RL_CAP * 8;
 }
 
-template <int MAXD, bool VEC, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_lane(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
-                   int k, WsView v, int32_t *__restrict__ lab_out,
-                   double *acc, int amode, int64_t base) {
-  if (v.hdr->qcount == 0) return;  // the screen resolved everything
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int dp = (int)round_up(d, 4);  // c32 row stride (dkm_util)
-  // (fp32 centres: global, scalar loads in resolve_lane)
-  int64_t *lists = (int64_t *)smem;
-  double *lds_acc = (double *)(lists + (BLOCK / 64) * RL_CAP);
-  __shared__ unsigned long long blk_count;
-  if (threadIdx.x == 0) blk_count = 0;
-  if (amode & AM_INLDS) zero_lds_acc(lds_acc, k, d);
-  const float cm =
-      (float)__longlong_as_double((long long)v.hdr->cmax_bits) * 1.000001f;
-  const AccTarget at = acc_target(amode, lds_acc, acc, k, d);
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  int64_t *wl = lists + (threadIdx.x >> 6) * RL_CAP;
-
-  auto resolve = [&](int64_t i) {
-    resolve_lane<MAXD, VEC, TX>(X, ldx, d, k, i, -lab_out[i] - 2, v.c32,
-                                v.cn32, dp,
-                                cm, v.ct64, lab_out, amode, at);
-  };
-
-  // Scan: 4 labels per lane (int4), 256 per wave step, the next step's
-  // labels in flight while this one resolves (a wave's list only holds
-  // samples of steps it has already scanned, so the prefetch is never stale).
-  // a0 aligns the int4 loads; lanes outside [base, n) read nothing.
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  const int64_t a0 =
-      base - (int64_t)(((uintptr_t)(lab_out + base) >> 2) & 3);
-  auto load4 = [&](int64_t c0, int (&o)[4]) {
-    const int64_t i0 = c0 + 4 * lane;
-    if (i0 >= base && i0 + 3 < n) {
-      const int4 q4 = *(const int4 *)(lab_out + i0);
-      o[0] = q4.x; o[1] = q4.y; o[2] = q4.z; o[3] = q4.w;
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        o[c] = (i0 + c >= base && i0 + c < n) ? lab_out[i0 + c] : 0;
-    }
-  };
-  unsigned long long mine = 0;
-  int cnt = 0;  // wave-uniform list length
-  int cur[4] = {0, 0, 0, 0};
-  int64_t c0 = a0 + wv * 256;
-  if (c0 < n) load4(c0, cur);
-  for (; c0 < n; c0 += nwv * 256) {
-    int nxt[4] = {0, 0, 0, 0};
-    if (c0 + nwv * 256 < n) load4(c0 + nwv * 256, nxt);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const unsigned long long mask = __ballot(cur[c] < 0);
-      if (cur[c] < 0)
-        wl[cnt + __popcll(mask & ((1ull << lane) - 1))] = c0 + 4 * lane + c;
-      const int add = __popcll(mask);
-      mine += add;
-      cnt += add;
-      if (cnt >= 64) {
-        wave_lds_sync();
-        resolve(wl[lane]);
-        const int rem = cnt - 64;
-        const int64_t tail = lane < rem ? wl[64 + lane] : 0;
-        wave_lds_sync();
-        if (lane < rem) wl[lane] = tail;
-        cnt = rem;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) cur[c] = nxt[c];
-  }
-  wave_lds_sync();
-  if (lane < cnt) resolve(wl[lane]);
-  recheck_finish_count(mine, &blk_count, v);
-  if (amode & AM_INLDS) flush_lds_acc(lds_acc, acc, k, d);
-}
-
-// The screen's per-wave lists (WsView::tlist/tcount, nseg segments): lane
-// per listed sample (resolve_lane), fp32 centres in LDS.  No label scan:
-// the work is proportional to the undecided samples only.
-template <int MAXD, bool VEC, class TX>
-__global__ void __launch_bounds__(BLOCK)
-    k_recheck_list(const TX *__restrict__ X, int d, int64_t ldx, int k,
-                   WsView v, int32_t *__restrict__ lab_out, double *acc,
-                   int amode, int64_t base, int nseg, int wave_all) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int dp = (int)round_up(d, 4);
-  // (fp32 centres: global, scalar loads in resolve_lane)
-  double *lds_acc = (double *)smem;
-  __shared__ unsigned long long blk_count;
-  // per wave: samples stage 1 left undecided, resolved 64 at a time (a
-  // lone stage-2 lane would otherwise hold its whole wave for a second pass)
-  __shared__ int2 dlist[BLOCK / 64][128];
-  if (threadIdx.x == 0) blk_count = 0;
-  if (amode & AM_INLDS) zero_lds_acc(lds_acc, k, d);
-  const float cm =
-      (float)__longlong_as_double((long long)v.hdr->cmax_bits) * 1.000001f;
-  const AccTarget at = acc_target(amode, lds_acc, acc, k, d);
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t wv = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t nwv = (int64_t)gridDim.x * (BLOCK / 64);
-  unsigned long long mine = 0;
-  int2 *dl = dlist[threadIdx.x >> 6];
-  int dcnt = 0;  // wave-uniform
-  auto stage2 = [&](int2 it) {
-    resolve_lane<MAXD, VEC, TX>(X, ldx, d, k, base + it.x, it.y, v.c32,
-                                v.cn32, dp,
-                                cm, v.ct64, lab_out, amode, at);
-  };
-  // wave_all: the samples go to the global list that k_recheck_wave
-  // resolves a wave per sample (v.smoved as (offset, prev) pairs; the
-  // per-wave LDS list only takes what overflows it).  Otherwise stage 1 runs
-  // here lane per sample and its leftovers are resolved 64 at a time (a long
-  // list holds many of them: a wave per sample cost 0.7 ms per C2 iteration)
-  int2 *s2l = (int2 *)v.smoved;
-  const uint32_t s2cap = (uint32_t)std::min<int64_t>(v.nq / 2, INT32_MAX);
-  // (segment, 64-sample batch) pairs dealt round-robin over all waves, batch
-  // index major: every resident wave gets work and the segments' row loads
-  // overlap across waves.  Wave-uniform loop; empty batches are skipped.
-  for (int64_t L = wv; L < (int64_t)nseg * (TL_CAP / 64); L += nwv) {
-    const int64_t sg = L % nseg;
-    const int t0 = (int)(L / nseg) * 64;
-    const int cnt = v.tcount[sg];
-    if (t0 == 0) mine += cnt;
-    if (t0 >= cnt) continue;
-    const int2 *e = v.tlist + sg * TL_CAP;
-    {
-      int2 it = make_int2(0, 0);
-      bool ok = true;
-      if (t0 + lane < cnt) {
-        it = e[t0 + lane];
-        // wave_all (short lists): every sample straight to k_recheck_wave
-        ok = !wave_all &&
-             resolve_lane<MAXD, VEC, TX, true>(X, ldx, d, k, base + it.x,
-                                               it.y, v.c32, v.cn32, dp, cm,
-                                               v.ct64, lab_out, amode, at);
-      }
-      unsigned long long m = __ballot(!ok);
-      if (m && wave_all) {
-        uint32_t pos = 0;
-        if (lane == 0) pos = atomicAdd(&v.hdr->s2count, (uint32_t)__popcll(m));
-        pos = (uint32_t)__shfl((int)pos, 0, 64);
-        const uint32_t p = pos + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (!ok && p < s2cap) s2l[p] = it;
-        m = __ballot(!ok && p >= s2cap);   // the rest: this wave, stage 2
-        ok = ok || p < s2cap;
-      }
-      if (!ok) dl[dcnt + __popcll(m & ((1ull << lane) - 1))] = it;
-      dcnt += __popcll(m);
-      if (dcnt >= 64) {
-        wave_lds_sync();
-        stage2(dl[lane]);
-        const int rem = dcnt - 64;
-        const int2 tail = lane < rem ? dl[64 + lane] : make_int2(0, 0);
-        wave_lds_sync();
-        if (lane < rem) dl[lane] = tail;
-        dcnt = rem;
-      }
-    }
-  }
-  wave_lds_sync();
-  if (lane < dcnt) stage2(dl[lane]);
-  recheck_finish_count(mine, &blk_count, v);
-  if (amode & AM_INLDS) flush_lds_acc(lds_acc, acc, k, d);
-}
+// k_recheck_lane and k_recheck_list, and their forms for a bounds call
+// (k_recheck_lane_bnd, k_recheck_list_bnd; d <= 32 only)
+#define RC_BND 0
+#include "dkm_recheck_kernels.inc"
+#undef RC_BND
+#define RC_BND 1
+#include "dkm_recheck_kernels.inc"
+#undef RC_BND
 
 // k_recheck_list's stage-2 samples (fp32 stage 1 could not decide them),
 // one wave per sample: lanes over centres (resolve_wave), so a sample with
@@ -539,17 +425,22 @@ static const void *recheck_lane_fn(bool vec) {
 template <class TX>
 int launch_recheck(const TX *X, int64_t end, int d, int64_t ldx, int k,
                    const WsView &v, int32_t *lab_out, double *acc,
-                   int acc_kind, bool vec, int64_t base, hipStream_t s) {
+                   int acc_kind, bool vec, int64_t base, hipStream_t s,
+                   const RcBnd *bnd) {
   const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
   const size_t fb = recheck_lane_lds(k, d);
   const bool lane = d <= 128 && fb <= LDS_BUDGET;
   const int maxd = d <= 32 ? 32 : d <= 64 ? 64 : 128;
+  if (bnd && !(lane && maxd == 32))
+    return fail(DKM_E_ARG, "exact re-check: bounds need d <= 32");
   const size_t fixed = lane ? fb : 0;
   const int amode = acc_mode(acc_kind, fixed + a_bytes <= LDS_BUDGET);
   const size_t lds = fixed + ((amode & AM_INLDS) ? a_bytes : 0);
   const bool small = d <= 128;
   const void *kf =
-      !lane   ? (small ? (const void *)k_recheck_exact<true, TX>
+      bnd     ? (vec ? (const void *)k_recheck_lane_bnd<32, true, TX>
+                     : (const void *)k_recheck_lane_bnd<32, false, TX>)
+      : !lane ? (small ? (const void *)k_recheck_exact<true, TX>
                        : (const void *)k_recheck_exact<false, TX>)
       : maxd == 32 ? recheck_lane_fn<32, TX>(vec)
       : maxd == 64 ? recheck_lane_fn<64, TX>(vec)
@@ -559,7 +450,14 @@ int launch_recheck(const TX *X, int64_t end, int d, int64_t ldx, int k,
   const unsigned g = (unsigned)std::max<int64_t>(
       1, std::min<int64_t>((int64_t)dev_info().cus * per_cu,
                            (waves + BLOCK / 64 - 1) / (BLOCK / 64)));
-  if (lane) {
+  if (bnd) {
+    if (vec)
+      k_recheck_lane_bnd<32, true, TX><<<g, BLOCK, lds, s>>>(
+          X, end, d, ldx, k, v, lab_out, acc, amode, base, *bnd);
+    else
+      k_recheck_lane_bnd<32, false, TX><<<g, BLOCK, lds, s>>>(
+          X, end, d, ldx, k, v, lab_out, acc, amode, base, *bnd);
+  } else if (lane) {
 #define DKM_RL(M)                                                            \
   (vec ? launch_recheck_lane_t<M, true, TX>(g, lds, s, X, end, d, ldx, k, v, \
                                             lab_out, acc, amode, base)       \
@@ -604,6 +502,25 @@ static int launch_list_t(const TX *X, int d, int64_t ldx, int k,
   return check_launch("list re-check (wave per sample)");
 }
 
+// launch_list_t for a bounds call: k_recheck_list_bnd, no wave-per-sample form
+template <bool VEC, class TX>
+static int launch_list_bnd_t(const TX *X, int d, int64_t ldx, int k,
+                             const WsView &v, int32_t *lab_out, double *acc,
+                             int amode, int64_t base, int nseg, size_t lds,
+                             hipStream_t s, const RcBnd &rb) {
+  const void *kf = (const void *)k_recheck_list_bnd<32, VEC, TX>;
+  const int per_cu = resident_blocks(kf, BLOCK, lds);
+  const int64_t units = (int64_t)nseg * (TL_CAP / 64);
+  const int64_t g = std::max<int64_t>(
+      1, std::min<int64_t>((int64_t)dev_info().cus * per_cu,
+                           (units + BLOCK / 64 - 1) / (BLOCK / 64)));
+  if (hipMemsetAsync(&v.hdr->s2count, 0, 4, s) != hipSuccess)
+    return fail(DKM_E_LAUNCH, "list re-check: counter reset");
+  k_recheck_list_bnd<32, VEC, TX><<<(unsigned)g, BLOCK, lds, s>>>(
+      X, d, ldx, k, v, lab_out, acc, amode, base, nseg, 0, rb);
+  return check_launch("list re-check (bounds)");
+}
+
 // Can the listed samples be resolved lane-per-sample (k_recheck_list)?
 bool list_ok(int64_t k, int64_t d) {
   return d <= 128 && recheck_lane_lds(k, d) <= LDS_BUDGET;
@@ -616,12 +533,22 @@ bool list_ok(int64_t k, int64_t d) {
 template <class TX>
 int launch_list(const TX *X, int d, int64_t ldx, int k, const WsView &v,
                 int32_t *lab_out, double *acc, int acc_kind, bool vec,
-                int64_t base, int nseg, hipStream_t s, bool wave_all) {
+                int64_t base, int nseg, hipStream_t s, bool wave_all,
+                const RcBnd *bnd) {
   const size_t fb = 0;  // centres are read from global (scalar loads)
   const size_t a_bytes = (size_t)lds_acc_len(k, d) * 8;
   const int amode = acc_mode(acc_kind, fb + a_bytes <= LDS_BUDGET);
   const size_t lds = fb + ((amode & AM_INLDS) ? a_bytes : 0);
   const int maxd = d <= 32 ? 32 : d <= 64 ? 64 : 128;
+  if (bnd) {
+    if (maxd != 32 || wave_all)
+      return fail(DKM_E_ARG, "list re-check: bounds need d <= 32");
+    return vec ? launch_list_bnd_t<true, TX>(X, d, ldx, k, v, lab_out, acc,
+                                             amode, base, nseg, lds, s, *bnd)
+               : launch_list_bnd_t<false, TX>(X, d, ldx, k, v, lab_out, acc,
+                                              amode, base, nseg, lds, s,
+                                              *bnd);
+  }
 #define DKM_LL(M)                                                            \
   (vec ? launch_list_t<M, true, TX>(X, d, ldx, k, v, lab_out, acc, amode,    \
                                     base, nseg, lds, s, wave_all)            \
@@ -635,10 +562,12 @@ int launch_list(const TX *X, int d, int64_t ldx, int k, const WsView &v,
 #define DKM_RECHECK_INST(TX)                                                 \
   template int launch_recheck<TX>(const TX *, int64_t, int, int64_t, int,    \
                                   const WsView &, int32_t *, double *, int,  \
-                                  bool, int64_t, hipStream_t);               \
+                                  bool, int64_t, hipStream_t,                \
+                                  const RcBnd *);                            \
   template int launch_list<TX>(const TX *, int, int64_t, int,                \
                                const WsView &, int32_t *, double *, int,     \
-                               bool, int64_t, int, hipStream_t, bool);
+                               bool, int64_t, int, hipStream_t, bool,        \
+                               const RcBnd *);
 DKM_RECHECK_INST(double)
 DKM_RECHECK_INST(float)
 #undef DKM_RECHECK_INST

@@ -755,6 +755,20 @@ int dkm_bounds_counters(const void *ws, int64_t *out, void *stream) {
   return 0;
 }
 
+int dkm_bounds_settled(const void *ws, int64_t *n_settled, void *stream) {
+  if (!ws || !n_settled) return fail(DKM_E_ARG, "bounds_settled: NULL");
+  WsHeader h;
+  hipError_t e = hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost,
+                                (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail((int)e, std::string("bounds_settled: ") +
+                            hipGetErrorString(e));
+  if (h.magic != WS_MAGIC) return fail(DKM_E_ARG, "bounds_settled: bad ws");
+  *n_settled = (int64_t)h.bnd_settled;
+  return 0;
+}
+
 int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
                      void *stream) {
   if (!ws || !out) return fail(DKM_E_ARG, "screen_lists: NULL");

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 5
+#define DKM_ABI_VERSION 6
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -267,7 +267,16 @@ int dkm_assign_delta_img_f32(const float *X, const void *image, int image_kind,
  * dkm_bounds_counters (host, syncs `stream`): over the workspace's life,
  * out[0] calls that ran the bounds pass, out[1] rows it left active, out[2]
  * rows it skipped, out[3] calls whose active rows were screened as a list
- * (out has 4 entries).                                                     */
+ * (out has 4 entries).
+ * A row the screen cannot decide goes to the exact re-check.  When the
+ * re-check's fp32 stage decides it (its two best fp32 scores over all k
+ * centres lie more than twice the fp32 bound apart), that stage writes the
+ * row's ub / lb from those scores; only a row left to the reference
+ * arithmetic (a tie or near-tie under fp32, a non-finite value) keeps
+ * (+inf, 0) and is screened again at the next call.  DKM_BOUNDS_SETTLE=0 in
+ * the environment (read at every call) leaves every re-checked row at
+ * (+inf, 0).  dkm_bounds_settled (host, syncs `stream`): the rows the
+ * re-check gave bounds to, over the workspace's life.                       */
 #define DKM_BOUNDS_INIT 1
 int dkm_bounds_ok(int64_t k, int64_t d);
 int dkm_assign_delta_bounds_f64(const double *X, const void *image,
@@ -285,6 +294,7 @@ int dkm_assign_delta_bounds_f32(const float *X, const void *image,
                                 float *ub, float *lb, int bounds_flags,
                                 void *stream);
 int dkm_bounds_counters(const void *ws, int64_t *out, void *stream);
+int dkm_bounds_settled(const void *ws, int64_t *n_settled, void *stream);
 
 /* acc[k*(d+1)] += [sums | counts] of the rows of X by labels (label < 0 or
  * >= k: skipped): the sums half of dkm_partial_sum for known labels.       */

@@ -5,7 +5,9 @@
 Runs bench.py's headline fit (on-device make_blobs, np.random.seed(0)
 initial centres, tol = 0) and prints, per iteration, the wall time and what
 dkm_bounds_counters gained: rows active, rows skipped, and whether the
-active rows were screened as a list or every row from the image.
+active rows were screened as a list or every row from the image, the rows
+the exact re-check took (the gain of rechecked()) and the rows it gave
+bounds to (dkm_bounds_settled; DKM_BOUNDS_SETTLE=0 turns that off).
 """
 import argparse
 import json
@@ -36,6 +38,8 @@ def main():
         ds._device_data(dev).drop_images()
         st = _Lloyd(ds, C0, 0.0, True, "auto", dev)
         rows, prev = [], (0, 0, 0, 0)
+        st.prepare()      # writes the workspace header the counters read
+        prev_r, prev_s = st.rechecked(), st.bounds_settled()
         for it in range(a.steps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -48,8 +52,11 @@ def main():
                          "active": c[1] - prev[1],
                          "skipped": c[2] - prev[2],
                          "active_frac": round((c[1] - prev[1]) / a.n, 5),
-                         "list_screen": c[3] - prev[3]})
+                         "list_screen": c[3] - prev[3],
+                         "rechecked": st.rechecked() - prev_r,
+                         "settled": st.bounds_settled() - prev_s})
             prev = c
+            prev_r, prev_s = st.rechecked(), st.bounds_settled()
     for r in rows:
         print(json.dumps(r))
 
