@@ -16,18 +16,21 @@ from dislib_amd._shard import shard_dataset, shard_range  # noqa: E402,F401
 
 
 def install_as_dislib():
-    """Alias ``dislib``, ``dislib.cluster``, ``dislib.data`` and
-    ``dislib.neighbors`` to this package (the k-means path, its data
-    containers and the kNN reuse of its distance primitive)."""
+    """Alias ``dislib``, ``dislib.cluster``, ``dislib.data``,
+    ``dislib.neighbors`` and ``dislib.preprocessing`` to this package (the
+    k-means path, its data containers, the kNN reuse of its distance
+    primitive and the StandardScaler)."""
     import types
-    from dislib_amd import cluster, data, neighbors
+    from dislib_amd import cluster, data, neighbors, preprocessing
     pkg = types.ModuleType("dislib")
     pkg.__path__ = []
     pkg.name = "dislib"
     pkg.cluster = cluster
     pkg.data = data
     pkg.neighbors = neighbors
+    pkg.preprocessing = preprocessing
     sys.modules["dislib"] = pkg
+    sys.modules["dislib.preprocessing"] = preprocessing
     sys.modules["dislib.neighbors"] = neighbors
     sys.modules["dislib.cluster"] = cluster
     sys.modules["dislib.data"] = data

@@ -182,6 +182,33 @@ class DeviceData:
         self._unbuilt = set()
         self._image_failed = set()
 
+    # -- a matrix that is already resident ----------------------------------
+    @classmethod
+    def from_matrix(cls, X, sizes):
+        """The image of a dense Dataset whose rows already are the resident
+        (n, d) fp32 / fp64 device matrix ``X`` (StandardScaler.transform's
+        output), cut into Subsets of ``sizes`` rows: nothing is uploaded or
+        copied."""
+        t = torch()
+        if X.dim() != 2 or X.dtype not in (t.float32, t.float64) or \
+                not X.is_cuda or sum(int(s) for s in sizes) != X.shape[0]:
+            raise ValueError("from_matrix: an (n, d) fp32 / fp64 device "
+                             "matrix and Subset sizes that sum to n")
+        dd = cls.__new__(cls)
+        dd.device = X.device
+        dd.images = {}
+        dd._unbuilt = set()
+        dd._image_failed = set()
+        dd.sizes = [int(s) for s in sizes]
+        dd.offsets = np.concatenate([[0], np.cumsum(dd.sizes)]).astype(
+            np.int64)
+        dd.n, dd.d = int(X.shape[0]), int(X.shape[1])
+        dd.sparse = False
+        dd.dtype = np.float32 if X.dtype == t.float32 else np.float64
+        dd.X = X.contiguous()
+        dd.int_input = False
+        return dd
+
     # -- helpers -----------------------------------------------------------
     def subset_slices(self):
         return [(int(a), int(b)) for a, b in zip(self.offsets[:-1],
@@ -542,6 +569,112 @@ def merge_tree(osum, acc, f32):
         ptr(osum.partials), osum.n_total, osum.len, ptr(osum.schedule),
         osum.n_ops, osum.k * (osum.len // osum.k - 1) if f32 else 0,
         ptr(osum.scratch), ptr(acc), stream_ptr()), "dkm_merge_tree")
+
+
+# ---------------------------------------------------------------------------
+# StandardScaler (dkm_scale.hip)
+# ---------------------------------------------------------------------------
+# rows whose loads a dkm_col_chain_* chain issues together (CH_U)
+SCALE_CHAIN_TILE = 16
+
+
+def scale_row_tile(d, dtype, vector=True):
+    """Rows one block of dkm_col_stats_* / dkm_scale_transform_* takes per
+    step on d columns (SC_B / pieces x SC_U of dkm_scale.hip): the sizes
+    around which the tests cut their Subsets."""
+    v = 16 // np.dtype(dtype).itemsize
+    cv = d // v if vector and d % v == 0 else d
+    return 256 // min(256, cv) * 4
+
+
+class ScaleSums:
+    """Buffers of a StandardScaler(sums="reference") fit: the Subset offsets
+    on the device, the partials of ALL ranks' Subsets (``n_total`` x (d + 1)
+    fp64, a row = [column sums | rows]; this rank fills its Subsets from slot
+    ``first``) and the merge schedule with its scratch -- the slot scheme of
+    :class:`OrderedSums` with one cluster, so :func:`merge_tree` takes it."""
+
+    def __init__(self, dd, first, n_total, schedule, n_ops, n_slots):
+        t = torch()
+        self.k, self.len = 1, dd.d + 1
+        self.n_local, self.first = len(dd.sizes), int(first)
+        self.n_total, self.n_ops = int(n_total), int(n_ops)
+        self.partials = _alloc("scale partials", self.n_total * self.len * 8,
+                               lambda: t.zeros(self.n_total * self.len,
+                                               dtype=t.float64,
+                                               device=dd.device))
+        self.scratch = t.empty(max(1, int(n_slots)) * self.len,
+                               dtype=t.float64, device=dd.device)
+        self.schedule = t.from_numpy(np.ascontiguousarray(
+            schedule, dtype=np.int32)).to(dd.device) if n_ops else None
+        self.offsets = t.from_numpy(np.ascontiguousarray(
+            dd.offsets, dtype=np.int64)).to(dd.device)
+        self.acc = t.empty(self.len, dtype=t.float64, device=dd.device)
+
+    def reset(self, sizes):
+        """Zero every slot (the other ranks' add +0.0) and write this rank's
+        row counts."""
+        t = torch()
+        self.partials.zero_()
+        if self.n_local:
+            own = self.partials.view(self.n_total, self.len)[
+                self.first:self.first + self.n_local]
+            own[:, self.len - 1] = t.tensor(
+                [float(s) for s in sizes], dtype=t.float64).to(own.device)
+
+
+def col_chain(dd, mean, ssum):
+    """This rank's slots of ``ssum.partials`` <- the per-Subset column sums
+    of x (``mean`` None) or (x - mean)^2 in the reference's order
+    (dkm_col_chain_*); ``mean``: a device vector of X's dtype."""
+    if ssum.n_local == 0:
+        return
+    so = _lib.lib()
+    fn = so.dkm_col_chain_f32 if dd.dtype == np.float32 else \
+        so.dkm_col_chain_f64
+    own = ssum.partials[ssum.first * ssum.len:]
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(mean), ptr(ssum.offsets), ssum.n_local, ptr(own),
+                  ssum.len, stream_ptr()), "dkm_col_chain")
+
+
+def scale_workspace(dd):
+    """The workspace of :func:`col_stats` for ``dd``."""
+    t = torch()
+    nb = int(_lib.lib().dkm_scale_workspace_bytes(dd.n, dd.d))
+    if nb == 0:
+        raise _lib.DkmError("dkm_scale_workspace_bytes: bad n/d")
+    return _alloc("scale", nb, lambda: t.empty(nb, dtype=t.uint8,
+                                               device=dd.device))
+
+
+def col_stats(dd, mean, ws, out):
+    """out[d] (fp64) <- the column sums of x (``mean`` None) or of
+    (x - mean)^2 (``mean``: device fp64[d]), dkm_col_stats_*."""
+    so = _lib.lib()
+    fn = so.dkm_col_stats_f32 if dd.dtype == np.float32 else \
+        so.dkm_col_stats_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(mean), ptr(ws), ws.numel(), ptr(out), stream_ptr()),
+               "dkm_col_stats")
+
+
+def scale_transform(dd, mean, var, Y):
+    """Y <- (X - mean) / sqrt(var) (dkm_scale_transform_*): ``mean`` / ``var``
+    device vectors of one dtype, Y of numpy's promotion of it and X's."""
+    t = torch()
+    so = _lib.lib()
+    s64 = mean.dtype == t.float64
+    if dd.dtype == np.float32:
+        fn = so.dkm_scale_transform_f32_f64 if s64 else \
+            so.dkm_scale_transform_f32
+    else:
+        fn = so.dkm_scale_transform_f64 if s64 else \
+            so.dkm_scale_transform_f64_f32
+    ld = dd.X.stride(0) if dd.n else dd.d
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, ld, ptr(mean), ptr(var), ptr(Y),
+                  Y.stride(0) if dd.n else dd.d, stream_ptr()),
+               "dkm_scale_transform")
 
 
 def add_(y, x, nonzero=None):

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DKM_LIB", os.path.join(_HERE, "libdkm.so"))
 
 # constants mirrored from include/dkm.h
-ABI_VERSION = 6
+ABI_VERSION = 7
 MODE_AUTO, MODE_EXACT, MODE_SCREEN32, MODE_BF16X3, MODE_BF16 = 0, 1, 2, 3, 4
 MODE_MASK, MODE_NOHINT, MODE_B1, MODE_TRANSLATE = 0xff, 0x100, 0x200, 0x400
 IMAGE_NONE, IMAGE_SINGLE, IMAGE_SPLIT, IMAGE_SORTED, IMAGE_GEMM = 0, 1, 2, 3, 4
@@ -84,6 +84,22 @@ SIGNATURES = {
     "dkm_ordered_sums_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64,
                                     _p, _sz, _p, _p]),
     "dkm_merge_tree": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _p]),
+    # StandardScaler: column statistics and the scaling
+    "dkm_scale_workspace_bytes": (_sz, [_i64, _i64]),
+    "dkm_col_stats_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _sz, _p, _p]),
+    "dkm_col_stats_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _sz, _p, _p]),
+    "dkm_col_chain_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _p,
+                                 _i64, _p]),
+    "dkm_col_chain_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _p,
+                                 _i64, _p]),
+    "dkm_scale_transform_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p,
+                                       _i64, _p]),
+    "dkm_scale_transform_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p,
+                                       _i64, _p]),
+    "dkm_scale_transform_f32_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p,
+                                           _i64, _p]),
+    "dkm_scale_transform_f64_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p,
+                                           _i64, _p]),
     "dkm_add_f64": (_i32, [_p, _p, _i64, _p]),
     "dkm_add_f64_nz": (_i32, [_p, _p, _i64, _p, _p]),
     "dkm_add_f64_dd": (_i32, [_p, _p, _p, _i64, _p, _p]),

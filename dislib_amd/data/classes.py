@@ -294,6 +294,20 @@ class Dataset(object):
                 _freeze(s.samples)
         return dd
 
+    def _adopt_device_data(self, dd):
+        """Make ``dd`` (a DeviceData whose rows are the Subsets' current
+        samples, e.g. ``DeviceData.from_matrix`` of the matrix they are
+        views or copies of) this Dataset's HBM image under the current
+        signature: the next device use uploads nothing."""
+        dd.signature = self._signature()
+        self._device = dd
+        self._host_image = None
+        self._samples = None
+        self._max_features = None
+        self._min_features = None
+        for s in self._subsets:
+            _freeze(s.samples)
+
     def _set_host_image(self, image):
         self._host_image = image
         self._host_image_sig = self._signature()

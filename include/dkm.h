@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 6
+#define DKM_ABI_VERSION 7
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -356,6 +356,76 @@ int dkm_ordered_sums_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
 int dkm_merge_tree(const double *partials, int64_t n_partials, int64_t len,
                    const int32_t *schedule, int64_t n_ops, int64_t sums_f32,
                    double *scratch, double *acc, void *stream);
+
+/* -----------------------------------------------------------------------
+ * StandardScaler on resident samples (reference
+ * dislib/preprocessing/classes.py).  X is fp64 (..._f64) or fp32 (..._f32),
+ * row-major with any ldx >= d; three pure streams over X, no floating-point
+ * atomic.  Compiled without fast-math and with IEEE fp32 divide and sqrt.
+ *
+ * dkm_col_stats_*: the fast column statistics.  out[d] (fp64) <- the column
+ * sums of x (mean = NULL: `_partial_sum`, classes.py:114-116, summed over
+ * all Subsets at once, which also replaces `_merge_sums`, :119-123) or of
+ * (x - mean[j])^2 (mean: device fp64[d]; `_partial_var` and `_merge_vars`,
+ * :126-134), accumulated in fp64 whatever X's dtype (fp32 samples are
+ * widened, which is exact; the mean stays fp64).  Every block writes its
+ * partial sums into ws (dkm_scale_workspace_bytes(n, d) bytes) and a second
+ * kernel adds them in a fixed order; the grid is a function of (n, d) only,
+ * so the same call gives the same bits every time.  The order is not the
+ * reference's: results agree with it to rounding, not bit for bit.  n = 0
+ * gives zeros.                                                            */
+size_t dkm_scale_workspace_bytes(int64_t n, int64_t d);
+int dkm_col_stats_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                      const double *mean, void *ws, size_t ws_bytes,
+                      double *out, void *stream);
+int dkm_col_stats_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                      const double *mean, void *ws, size_t ws_bytes,
+                      double *out, void *stream);
+/* dkm_col_chain_*: the same statistics in the reference's order, for every
+ * Subset at once: `np.sum(subset.samples, axis=0)` (classes.py:116) when
+ * mean = NULL, `np.sum((subset.samples - mean) ** 2, axis=0)` (:129) else.
+ * subset_off (device int64[n_subsets + 1]) cuts the rows as in
+ * dkm_ordered_sums_*.  Each (Subset, column) is ONE sequential chain in
+ * ascending row order from +0.0 (numpy's order for a C-contiguous matrix of
+ * two or more columns), in the samples' dtype: fp32 chains round every add
+ * to fp32, and the subtraction and the square are each rounded in that
+ * dtype before the add (mean: a device vector of X's dtype).  Subset s is
+ * written to partials[s * ldp .. s * ldp + d) (fp64; fp32 results are
+ * widened, which is exact; ldp >= d, the other elements are untouched), the
+ * layout dkm_merge_tree folds (`_merge_sums`, `_merge_vars`, :119-134).  No
+ * result depends on a grid or block size.  The parallelism is n_subsets x d
+ * chains: few Subsets are slow by definition of the order.                */
+int dkm_col_chain_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                      const double *mean, const int64_t *subset_off,
+                      int64_t n_subsets, double *partials, int64_t ldp,
+                      void *stream);
+int dkm_col_chain_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                      const float *mean, const int64_t *subset_off,
+                      int64_t n_subsets, double *partials, int64_t ldp,
+                      void *stream);
+/* dkm_scale_transform_*: Y = (X - mean) / sqrt(var), element by element
+ * (`_transform`, classes.py:144-147).  The sqrt is taken once per column in
+ * the statistics' dtype, the subtraction and the one divide per element in
+ * numpy's promotion of the two dtypes, all IEEE correctly rounded; a zero
+ * variance gives numpy's NaN / inf.  _f64: fp64 samples and statistics;
+ * _f32: fp32 both, fp32 Y; _f32_f64: fp32 samples, fp64 statistics, fp64 Y;
+ * _f64_f32: fp64 samples, fp32 statistics (an fp32 sqrt), fp64 Y.  Y is
+ * n x d with leading dimension ldy >= d and may be X itself (same ld).    */
+int dkm_scale_transform_f64(const double *X, int64_t n, int64_t d,
+                            int64_t ldx, const double *mean,
+                            const double *var, double *Y, int64_t ldy,
+                            void *stream);
+int dkm_scale_transform_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                            const float *mean, const float *var, float *Y,
+                            int64_t ldy, void *stream);
+int dkm_scale_transform_f32_f64(const float *X, int64_t n, int64_t d,
+                                int64_t ldx, const double *mean,
+                                const double *var, double *Y, int64_t ldy,
+                                void *stream);
+int dkm_scale_transform_f64_f32(const double *X, int64_t n, int64_t d,
+                                int64_t ldx, const float *mean,
+                                const float *var, double *Y, int64_t ldy,
+                                void *stream);
 
 /* y[i] += x[i] (device, fp64): acc_new = acc_old + delta.                  */
 int dkm_add_f64(double *y, const double *x, int64_t n, void *stream);

@@ -1,0 +1,365 @@
+"""GPU tests of StandardScaler (dkm_scale.hip): the reference mode against
+the reference's goldens bit for bit, the three kernels' edges through the C
+ABI against the numpy restatement, the fast mode within the project's
+tolerances, determinism, and the residency of the scaled Dataset."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from dislib_amd import _device, _lib
+from dislib_amd.cluster import KMeans
+from dislib_amd.data import Dataset, Subset, load_data
+from dislib_amd.preprocessing import StandardScaler
+from oracle import kmeans_oracle as orc
+from tests import scaler_ref as sr
+from tests.conftest import load_golden
+from tests.test_scaler_host import CASES, check_scaled, same
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    torch.cuda.set_device(0)
+
+
+def dataset(x, sizes):
+    ds = Dataset(n_features=x.shape[1])
+    for block in sr.split(x, sizes):
+        ds.append(Subset(block))
+    return ds
+
+
+def scaled(ds):
+    return np.concatenate([np.asarray(s.samples) for s in ds])
+
+
+def run(x, sizes, **kw):
+    ds = dataset(x, sizes)
+    sc = StandardScaler(**kw)
+    assert sc.fit_transform(ds) is None
+    return sc.mean_, sc.var_, scaled(ds)
+
+
+# ---------------------------------------------------------------------------
+# reference mode against the goldens
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CASES,
+                         ids=["%s_%sa%d" % (c[0], c[1], c[5]) for c in CASES])
+def test_reference_mode_equals_the_golden(case):
+    name, key, k, x, sizes, arity = case
+    g = load_golden(name)
+    mean, var, y = run(x, sizes, arity=arity, sums="reference")
+    assert mean.shape == var.shape == (x.shape[1],)
+    assert same(mean, g[k + "mean"]) and same(var, g[k + "var"])
+    check_scaled(g, k, y)
+    again = run(x, sizes, arity=arity, sums="reference")
+    for a, b in zip((mean, var, y), again):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_reference_mode_s07_fp32_data_fp64_statistics():
+    g = load_golden("s07")
+    (_, x, sizes, _), = sr.inputs("s07")
+    sc = StandardScaler(sums="reference")
+    assert sc.fit(dataset(x, sizes)) is None
+    assert same(sc.mean_, g["mean"]) and same(sc.var_, g["var"])
+    x32, sizes32 = sr.s07_input()
+    out = []
+    for _ in range(2):
+        ds = dataset(x32, sizes32)
+        assert sc.transform(ds) is None
+        out.append(scaled(ds))
+    check_scaled(g, "", out[0])
+    assert out[0].tobytes() == out[1].tobytes()
+
+
+def test_reference_mode_refusals():
+    x = np.random.RandomState(0).standard_normal((40, 3))
+    with pytest.raises(ValueError, match="arity"):
+        StandardScaler(arity=1, sums="reference").fit(dataset(x, [20, 20]))
+    StandardScaler(arity=1, sums="reference").fit(dataset(x, [40]))
+    with pytest.raises(NotImplementedError, match="pairwise"):
+        StandardScaler(sums="reference").fit(dataset(x[:, :1], [20, 20]))
+
+
+# ---------------------------------------------------------------------------
+# kernel edges through the C ABI
+# ---------------------------------------------------------------------------
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _padded(x, ld):
+    """x in a device buffer with leading dimension ld (NaN in the padding:
+    a kernel that reads it shows)."""
+    buf = torch.full((max(1, x.shape[0]), ld), float("nan"),
+                     dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
+    buf[:x.shape[0], :x.shape[1]] = torch.from_numpy(x).cuda()
+    return buf
+
+
+def _edge_sizes(d, dtype, vector):
+    sizes = []
+    for r in (_device.SCALE_CHAIN_TILE,
+              _device.scale_row_tile(d, dtype, vector)):
+        sizes += [r - 1, r, r + 1, 2 * r + 1]
+    # more than one block of the streams (their grid: n d / 16384 blocks)
+    return sizes + [0, 3 * 16384 // d + 5]
+
+
+@pytest.mark.parametrize("pad", [0, 3, 4])
+@pytest.mark.parametrize("d", [2, 3, 32, 33, 64, 130])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_kernel_edges_against_the_restatement(dtype, d, pad):
+    so = _lib.lib()
+    f32 = dtype == np.float32
+    v = 16 // np.dtype(dtype).itemsize
+    vector = d % v == 0 and (d + pad) % v == 0
+    sizes = _edge_sizes(d, dtype, vector)
+    n, S = sum(sizes), len(sizes)
+    rs = np.random.RandomState(1000 * d + pad)
+    x = (rs.standard_normal((n, d)) * 3.0 + rs.uniform(-4, 4, d)).astype(dtype)
+    blocks = sr.split(x, sizes)
+    X = _padded(x, d + pad)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(
+        np.int64)).cuda()
+    mean = x.mean(axis=0, dtype=np.float64)
+
+    # chains: x and (x - mean)^2 in the samples' dtype, exact
+    chain = so.dkm_col_chain_f32 if f32 else so.dkm_col_chain_f64
+    ldp = d + 1
+    for m in (None, mean.astype(dtype)):
+        part = torch.full((S, ldp), -7.0, dtype=torch.float64, device="cuda")
+        md = torch.from_numpy(m).cuda() if m is not None else None
+        _lib.check(chain(_p(X), n, d, d + pad, _p(md), _p(off), S, _p(part),
+                         ldp, st), "chain")
+        got = part.cpu().numpy()
+        assert (got[:, d] == -7.0).all()          # beyond d: untouched
+        for s, b in enumerate(blocks):
+            want = sr.chain(b if m is None else (b - m) ** 2)
+            assert want.dtype == dtype
+            assert np.array_equal(got[s, :d], want.astype(np.float64)), s
+
+    # fast statistics: fp64 sums in another order.  Any order of n fp64 adds
+    # is within (n - 1) 2^-53 sum|t| of the exact sum; a term (x - m)^2 adds
+    # 3 roundings of its own: (n + 3) 2^-53 sum|t|, doubled for the
+    # yardstick's own (pairwise) error
+    stats = so.dkm_col_stats_f32 if f32 else so.dkm_col_stats_f64
+    nws = so.dkm_scale_workspace_bytes(n, d)
+    ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
+    x64 = x.astype(np.float64)
+    for m in (None, mean):
+        out = torch.full((d,), -7.0, dtype=torch.float64, device="cuda")
+        md = torch.from_numpy(m).cuda() if m is not None else None
+        res = []
+        for _ in range(2):
+            _lib.check(stats(_p(X), n, d, d + pad, _p(md), _p(ws), nws,
+                             _p(out), st), "stats")
+            res.append(out.cpu().numpy())
+        assert res[0].tobytes() == res[1].tobytes()
+        terms = x64 if m is None else (x64 - m) ** 2
+        bound = 2 * (n + 3) * 2.0 ** -53 * np.abs(terms).sum(axis=0)
+        assert (np.abs(res[0] - terms.sum(axis=0)) <= bound).all()
+
+    # the scaling: numpy's own correctly rounded arithmetic, exact
+    var = ((x64 - mean) ** 2).mean(axis=0)
+    for sdt, name in ((dtype, "f32" if f32 else "f64"),
+                      (np.float64 if f32 else np.float32,
+                       "f32_f64" if f32 else "f64_f32")):
+        m, w = mean.astype(sdt), var.astype(sdt)
+        want = (x - m) / np.sqrt(w)
+        Y = torch.full((n, d + pad), -7.0, device="cuda",
+                       dtype=torch.from_numpy(want[:0]).dtype)
+        fn = getattr(so, "dkm_scale_transform_" + name)
+        md, wd = torch.from_numpy(m).cuda(), torch.from_numpy(w).cuda()
+        _lib.check(fn(_p(X), n, d, d + pad, _p(md), _p(wd), _p(Y), d + pad,
+                      st), name)
+        got = Y.cpu().numpy()
+        assert got.dtype == want.dtype
+        assert np.array_equal(got[:, :d], want), name
+        assert (got[:, d:] == -7.0).all()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_kernels_take_zero_rows(dtype):
+    so = _lib.lib()
+    f32 = dtype == np.float32
+    d, S = 5, 3
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    off = torch.zeros(S + 1, dtype=torch.int64, device="cuda")
+    part = torch.full((S, d), -7.0, dtype=torch.float64, device="cuda")
+    chain = so.dkm_col_chain_f32 if f32 else so.dkm_col_chain_f64
+    _lib.check(chain(None, 0, d, d, None, _p(off), S, _p(part), d, st), "c")
+    assert (part.cpu().numpy() == 0).all()
+    out = torch.full((d,), -7.0, dtype=torch.float64, device="cuda")
+    nws = so.dkm_scale_workspace_bytes(0, d)
+    assert nws > 0
+    ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
+    stats = so.dkm_col_stats_f32 if f32 else so.dkm_col_stats_f64
+    _lib.check(stats(None, 0, d, d, None, _p(ws), nws, _p(out), st), "s")
+    assert (out.cpu().numpy() == 0).all()
+    one = torch.ones(d, dtype=torch.from_numpy(np.zeros(0, dtype)).dtype,
+                     device="cuda")
+    fn = so.dkm_scale_transform_f32 if f32 else so.dkm_scale_transform_f64
+    _lib.check(fn(None, 0, d, d, _p(one), _p(one), None, d, st), "t")
+    torch.cuda.synchronize()
+
+
+# ---------------------------------------------------------------------------
+# fast mode
+# ---------------------------------------------------------------------------
+FAST64 = [c for c in CASES if c[0] in ("s01", "s02", "s06")]
+
+
+@pytest.mark.parametrize("case", FAST64,
+                         ids=["%s_%sa%d" % (c[0], c[1], c[5]) for c in FAST64])
+def test_fast_mode_fp64_is_within_the_centre_tolerance(case):
+    name, key, k, x, sizes, arity = case
+    g = load_golden(name)
+    gm, gv = g[k + "mean"], g[k + "var"]
+    mean, var, y = run(x, sizes, arity=arity)
+    assert mean.dtype == var.dtype == y.dtype == np.float64
+    std = np.sqrt(gv)
+    assert (np.abs(mean - gm) <= 1e-9 * np.maximum(np.abs(gm), std)).all()
+    assert (np.abs(var - gv) <= 1e-9 * np.maximum(np.abs(gv), std)).all()
+    z = (x - gm) / std        # the golden's scaled matrix (test_scaler_host)
+    assert (np.abs(y - z) <= 1e-9 * np.maximum(np.abs(z), 1.0)).all()
+
+
+def test_fast_mode_fp32_against_fp64_numpy():
+    """fp32 samples: the fast path accumulates in fp64 and rounds mean_ and
+    var_ to fp32 once, so both are within 2^-22 relative of an fp64 numpy
+    evaluation of the fp32 data.  The scaled fp32 values carry the rounding
+    of mean_ (2^-24 |m| / sd), of x - m, of var_ and its sqrt (1.5 x 2^-24
+    |z|) and of the divide (2^-24 |z| each): 2^-24 (|m| / sd + 4 |z|)."""
+    (_, x, sizes, _), = sr.inputs("s03")
+    mean, var, y = run(x, sizes)
+    assert mean.dtype == var.dtype == y.dtype == np.float32
+    m64, v64 = sr.fit_fp64(x)
+    sd = np.sqrt(v64)
+    assert (np.abs(mean - m64) <= 2.0 ** -22 * np.maximum(np.abs(m64),
+                                                         sd)).all()
+    assert (np.abs(var - v64) <= 2.0 ** -22 * v64).all()
+    z = (x.astype(np.float64) - m64) / sd
+    assert (np.abs(y - z) <= 2.0 ** -24 * (np.abs(m64) / sd +
+                                           4 * np.abs(z))).all()
+
+
+def test_fast_mode_is_deterministic_and_takes_one_column():
+    (_, x, sizes, _), = sr.inputs("s06")[:1]
+    a, b = run(x, sizes), run(x, sizes)
+    for u, v in zip(a, b):
+        assert u.tobytes() == v.tobytes()
+    col = np.ascontiguousarray(x[:, :1])
+    mean, var, y = run(col, sizes)
+    m64, v64 = sr.fit_fp64(col)
+    assert mean.shape == (1,) and y.shape == col.shape
+    assert (np.abs(mean - m64) <= 1e-9 * np.maximum(np.abs(m64), 1)).all()
+    assert (np.abs(var - v64) <= 1e-9 * v64).all()
+    z = (col - m64) / np.sqrt(v64)
+    assert (np.abs(y - z) <= 1e-9 * np.maximum(np.abs(z), 1.0)).all()
+    with pytest.raises(NotImplementedError, match="pairwise"):
+        run(col, sizes, sums="reference")
+
+
+def test_integer_samples_fast_mode():
+    (_, x, sizes, _), = sr.inputs("s04")
+    g = load_golden("s04")
+    mean, var, y = run(x, sizes)
+    assert y.dtype == np.float64
+    assert (np.abs(mean - g["mean"]) <= 1e-9 * np.sqrt(g["var"])).all()
+    assert (np.abs(y - g["y"]) <= 1e-9 * np.maximum(np.abs(g["y"]), 1)).all()
+
+
+# ---------------------------------------------------------------------------
+# residency
+# ---------------------------------------------------------------------------
+def _blobs():
+    (_, x, _, _), = sr.inputs("s01")
+    return x[:3000]
+
+
+def _oracle_labels(z):
+    ref = orc.OracleKMeans(n_clusters=3, max_iter=4, tol=0, random_state=0)
+    return ref.fit([z[i:i + 500] for i in range(0, len(z), 500)],
+                   set_labels=True)
+
+
+def test_scaled_host_dataset_stays_resident_for_the_fit():
+    x = _blobs()
+    keep = x.copy()
+    ds = load_data(x, subset_size=500)
+    sc = StandardScaler(sums="reference")
+    sc.fit_transform(ds)
+    assert np.array_equal(x, keep)                  # never written
+    mean, var = sr.fit(sr.split(x, sr.blocks(3000, 500)))
+    z = np.concatenate(sr.transform([x], mean, var))
+    for i, s in enumerate(ds):
+        assert isinstance(s.samples, np.ndarray)
+        assert np.array_equal(s.samples, z[500 * i:500 * (i + 1)])
+    dd = ds._device
+    assert dd is not None and dd.signature == ds._signature()
+    Y, p = dd.X, dd.X.data_ptr()
+    km = KMeans(n_clusters=3, max_iter=4, tol=0, random_state=0)
+    km.fit_predict(ds)
+    assert ds._device_data() is dd and dd.X is Y and Y.data_ptr() == p
+    assert np.array_equal(Y.cpu().numpy(), z)
+    assert np.array_equal(ds.labels_int32(), _oracle_labels(z))
+    km.predict(ds)
+    assert ds._device_data() is dd
+
+
+def test_scaled_device_dataset_holds_views_of_one_matrix():
+    x = _blobs()
+    xd = torch.from_numpy(x).cuda()
+    ds = load_data(xd, subset_size=500)
+    sc = StandardScaler(sums="reference")
+    sc.fit_transform(ds)
+    assert torch.equal(xd.cpu(), torch.from_numpy(x))     # caller's: unchanged
+    mean, var = sr.fit(sr.split(x, sr.blocks(3000, 500)))
+    z = np.concatenate(sr.transform([x], mean, var))
+    dd = ds._device
+    Y = dd.X
+    assert Y.data_ptr() != xd.data_ptr()
+    for i, s in enumerate(ds):
+        assert isinstance(s.samples, torch.Tensor) and s.samples.is_cuda
+        assert s.samples.data_ptr() == Y[500 * i:].data_ptr()
+        assert np.array_equal(s.samples.cpu().numpy(),
+                              z[500 * i:500 * (i + 1)])
+    km = KMeans(n_clusters=3, max_iter=4, tol=0, random_state=0)
+    km.fit_predict(ds)
+    assert ds._device_data() is dd and dd.X is Y
+    assert np.array_equal(ds.labels_int32(), _oracle_labels(z))
+
+
+def test_transform_drops_cached_images_and_keeps_labels():
+    x = _blobs()
+    ds = load_data(x, subset_size=500)
+    km = KMeans(n_clusters=3, max_iter=2, tol=0, random_state=0)
+    km.fit_predict(ds)
+    labels = ds.labels_int32().copy()
+    old = ds._device_data()
+    old.screen_image(3, _lib.MODE_AUTO)
+    if not old.images:       # (k, d) screens without one: any cached buffer
+        old.images[_lib.IMAGE_SPLIT] = torch.empty(64, dtype=torch.uint8,
+                                                   device="cuda")
+    sc = StandardScaler()
+    sc.fit_transform(ds)
+    assert old.images == {} and ds._device.images == {}
+    assert ds._device is not old
+    assert np.array_equal(ds.labels_int32(), labels)
+
+
+def test_feature_mismatch_is_a_value_error():
+    x = _blobs()
+    sc = StandardScaler()
+    sc.fit(load_data(x, subset_size=1000))
+    with pytest.raises(ValueError, match="features"):
+        sc.transform(load_data(np.ascontiguousarray(x[:, :5]),
+                               subset_size=1000))
