@@ -15,6 +15,7 @@ from sklearn.datasets import make_blobs
 
 from oracle import kmeans_oracle as orc
 from tests.conftest import load_golden
+from tests.dense_f32_ref import sum_bound
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -100,10 +101,13 @@ def test_gemm_partial_sum_vs_oracle(n, d, k, seed, gmode):
 def test_gemm_fp32_samples(gmode):
     x, C = _data(3000, 300, 100, 7, np.float32)
     lab, sums, cnt, _ = _run(x, C, mode=gmode)
-    rl, rs, rc = orc.partial_sum(x, C)
+    # fp64 sums of the exactly upcast rows against the oracle's, within the
+    # distance between two fp64 sums of the same terms in different orders
+    rl, rs, rc = orc.partial_sum(x.astype(np.float64), C)
+    assert np.array_equal(rl, orc.predict_labels(x, C))
     assert np.array_equal(lab, rl)
     assert np.array_equal(cnt, rc.astype(np.float64))
-    _close(sums, rs, 1e-4)
+    assert (np.abs(sums - rs) <= sum_bound(x, rl, 100)).all()
 
 
 @pytest.mark.parametrize("d,k", [(200, 300), (1024, 600)])

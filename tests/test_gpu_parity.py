@@ -16,6 +16,7 @@ from sklearn.datasets import make_blobs
 
 from oracle import kmeans_oracle as orc
 from tests.conftest import load_golden
+from tests.dense_f32_ref import sum_bound
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -500,11 +501,17 @@ def test_fp32_partial_sum_labels():
     rng = np.random.default_rng(8)
     x = (rng.standard_normal((20000, 24)) * 4).astype(np.float32)
     C = rng.standard_normal((30, 24)) * 4
+    # the kernels add the exactly upcast rows in fp64: the reference is the
+    # oracle's fp64-accumulated sums, the bound the distance between two
+    # fp64 sums of the same terms in different orders
+    rl, rs, rc = orc.partial_sum(x.astype(np.float64), C)
+    assert np.array_equal(rl, orc.predict_labels(x, C))
+    bound = sum_bound(x, rl, 30)
     for mode in MODES:
         lab, sums, cnt, _ = _partial_sum_gpu(x, C, mode)
-        rl, rs, rc = orc.partial_sum(x, C)
         assert np.array_equal(lab, rl)
-        _close(sums, rs, 1e-4)
+        assert np.array_equal(cnt, rc.astype(np.float64))
+        assert (np.abs(sums - rs) <= bound).all(), mode
 
 
 def test_make_blobs_generator_matches_oracle():
