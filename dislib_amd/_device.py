@@ -677,6 +677,88 @@ def scale_transform(dd, mean, var, Y):
                "dkm_scale_transform")
 
 
+# ---------------------------------------------------------------------------
+# GaussianMixture (dkm_gm.hip)
+# ---------------------------------------------------------------------------
+# rows of a dkm_gm_estep_* wave tile / block and of an M-step MFMA step: the
+# sizes around which the tests cut their row counts
+GM_TILE = 16
+GM_MSTEP_ROWS = 4
+
+
+def gm_estep_block(d):
+    """Rows one block of dkm_gm_estep_* takes on d columns."""
+    return 64 if 64 < d <= 128 else 128
+
+
+def gm_workspace(dd, k):
+    """The workspace of the three GaussianMixture passes on ``dd``."""
+    t = torch()
+    nb = int(_lib.lib().dkm_gm_workspace_bytes(dd.n, dd.d, int(k)))
+    if nb == 0:
+        raise _lib.DkmError("dkm_gm_workspace_bytes: bad n/d/k")
+    return _alloc("gm", nb, lambda: t.empty(nb, dtype=t.uint8,
+                                            device=dd.device))
+
+
+def alloc_resp(dd, k):
+    """The resident (n, k) fp64 responsibilities; ValueError when they would
+    leave less than 4 GiB of HBM free (the rule of sums="reference")."""
+    t = torch()
+    nb = 8 * dd.n * int(k)
+    free = t.cuda.mem_get_info(dd.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        raise ValueError(
+            "GaussianMixture keeps the responsibilities resident: %d x %d "
+            "fp64 need %.2f GiB of HBM, and %.2f GiB are free (4 GiB stay "
+            "free)" % (dd.n, k, nb / 2.0 ** 30, free / 2.0 ** 30))
+    return _alloc("resp", nb, lambda: t.empty((dd.n, int(k)),
+                                              dtype=t.float64,
+                                              device=dd.device))
+
+
+def gm_onehot(labels, resp):
+    """resp[i, c] <- labels[i] == c (``labels``: device int32)."""
+    n, k = resp.shape
+    _lib.check(_lib.lib().dkm_gm_onehot(ptr(labels), n, k, ptr(resp),
+                                        stream_ptr()), "dkm_gm_onehot")
+
+
+def gm_estep(dd, means, pc, ldw, upper, ws, resp, labels, out):
+    """resp, labels (device int64 or None) and out[0] = sum of the rows'
+    log_prob_norm for the device parameters ``means`` (k, d), ``pc``
+    (k, d, d) and ``ldw`` = log det + log weights (k); dkm_gm_estep_*."""
+    so = _lib.lib()
+    fn = so.dkm_gm_estep_f32 if dd.dtype == np.float32 else \
+        so.dkm_gm_estep_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(means), ptr(pc), ptr(ldw), means.shape[0],
+                  _lib.GM_UPPER if upper else 0, ptr(ws), ws.numel(),
+                  ptr(resp), ptr(labels), ptr(out), stream_ptr()),
+               "dkm_gm_estep")
+
+
+def gm_mstep_sums(dd, resp, ws, out):
+    """out (fp64, k + k d) <- [nk | resp^T X], dkm_gm_mstep_sums_*."""
+    so = _lib.lib()
+    fn = so.dkm_gm_mstep_sums_f32 if dd.dtype == np.float32 else \
+        so.dkm_gm_mstep_sums_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(resp), resp.shape[1], ptr(ws), ws.numel(), ptr(out),
+                  stream_ptr()), "dkm_gm_mstep_sums")
+
+
+def gm_mstep_cov(dd, resp, means, ws, cov):
+    """cov (k, d, d) <- sum_n r (x - mean)(x - mean)^T around the device
+    ``means``, dkm_gm_mstep_cov_*."""
+    so = _lib.lib()
+    fn = so.dkm_gm_mstep_cov_f32 if dd.dtype == np.float32 else \
+        so.dkm_gm_mstep_cov_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0) if dd.n else dd.d,
+                  ptr(resp), ptr(means), resp.shape[1], ptr(ws), ws.numel(),
+                  ptr(cov), stream_ptr()), "dkm_gm_mstep_cov")
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DKM_LIB", os.path.join(_HERE, "libdkm.so"))
 
 # constants mirrored from include/dkm.h
-ABI_VERSION = 7
+ABI_VERSION = 8
 MODE_AUTO, MODE_EXACT, MODE_SCREEN32, MODE_BF16X3, MODE_BF16 = 0, 1, 2, 3, 4
 MODE_MASK, MODE_NOHINT, MODE_B1, MODE_TRANSLATE = 0xff, 0x100, 0x200, 0x400
 IMAGE_NONE, IMAGE_SINGLE, IMAGE_SPLIT, IMAGE_SORTED, IMAGE_GEMM = 0, 1, 2, 3, 4
@@ -19,6 +19,7 @@ IMAGE_BUILD = 0x100   # kind flag: build the allocated image during the call
 SUMS_F64, SUMS_F32, SUMS_RECIP = 0, 1, 2
 PREP_CSR = 1
 BOUNDS_INIT = 1
+GM_UPPER = 1
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -100,6 +101,21 @@ SIGNATURES = {
                                            _i64, _p]),
     "dkm_scale_transform_f64_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p,
                                            _i64, _p]),
+    # GaussianMixture: E-step and the two M-step passes (fp64 MFMA)
+    "dkm_gm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dkm_gm_estep_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i32,
+                                _p, _sz, _p, _p, _p, _p]),
+    "dkm_gm_estep_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i32,
+                                _p, _sz, _p, _p, _p, _p]),
+    "dkm_gm_mstep_sums_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,
+                                     _p, _p]),
+    "dkm_gm_mstep_sums_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,
+                                     _p, _p]),
+    "dkm_gm_mstep_cov_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _p,
+                                    _sz, _p, _p]),
+    "dkm_gm_mstep_cov_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _p,
+                                    _sz, _p, _p]),
+    "dkm_gm_onehot": (_i32, [_p, _i64, _i64, _p, _p]),
     "dkm_add_f64": (_i32, [_p, _p, _i64, _p]),
     "dkm_add_f64_nz": (_i32, [_p, _p, _i64, _p, _p]),
     "dkm_add_f64_dd": (_i32, [_p, _p, _p, _i64, _p, _p]),

@@ -1,3 +1,4 @@
+from dislib_amd.cluster.gm import GaussianMixture
 from dislib_amd.cluster.kmeans import KMeans
 
-__all__ = ['KMeans']
+__all__ = ['KMeans', 'GaussianMixture']

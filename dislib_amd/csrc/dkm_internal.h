@@ -32,6 +32,7 @@ int preload_sums();
 int preload_neighbors();
 int preload_ordered();
 int preload_scale();
+int preload_gm();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -58,6 +59,7 @@ int tu_flags_sums();
 int tu_flags_neighbors();
 int tu_flags_ordered();
 int tu_flags_scale();
+int tu_flags_gm();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

@@ -232,6 +232,24 @@ class Dataset(object):
                 parts.append(np.asarray(s._labels).astype(np.int32))
         return np.concatenate(parts) if parts else None
 
+    def _device_labels(self):
+        """The int32 device tensor behind the Subsets' labels when all of
+        them still are the rows, in order, of one device assignment (a
+        ``fit_predict`` / ``predict`` whose labels nobody has read or
+        replaced yet); else None."""
+        src, off = None, 0
+        for s in self._subsets:
+            if s._pending is None:
+                return None
+            cur, a, b = s._pending
+            if (src is not None and cur is not src) or a != off or \
+                    b - a != _nrows(s.samples):
+                return None
+            src, off = cur, b
+        if src is None or src.tensor.shape[0] != off:
+            return None
+        return src.tensor
+
     def _reset_attributes(self):
         self._max_features = None
         self._min_features = None

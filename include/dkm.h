@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 7
+#define DKM_ABI_VERSION 8
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -426,6 +426,57 @@ int dkm_scale_transform_f64_f32(const double *X, int64_t n, int64_t d,
                                 int64_t ldx, const float *mean,
                                 const float *var, double *Y, int64_t ldy,
                                 void *stream);
+
+/* ------------------------------------------------------------------------
+ * GaussianMixture, covariance_type='full' (dislib/cluster/gm/base.py): the
+ * three passes of an EM iteration over resident rows, all fp64 on the f64
+ * MFMA (fp32 rows are widened in the loads, as numpy promotes them).  No
+ * floating-point atomic: partials of fixed row ranges added in a fixed
+ * order, grids that depend on (n, d, k) only -- the same input gives the
+ * same bits from run to run.  One workspace serves the three.
+ * --------------------------------------------------------------------- */
+#define DKM_GM_UPPER 1 /* every precisions_chol[c] is upper triangular: the
+                          E-step skips the rows below each 16-column panel  */
+size_t dkm_gm_workspace_bytes(int64_t n, int64_t d, int64_t k);
+/* Replaces _estimate_responsibilities (:201-237) for every row:
+ *   y = (x - means[c]) . precisions_chol[c],
+ *   wlp[c] = -(d log(2 pi) + sum y^2) / 2 + log_det_w[c]
+ *            (log_det_w = log det chol + log weight, k values),
+ *   lse = max + log(sum_c exp(wlp[c] - max)), resp[row][c] = exp(wlp[c] - lse)
+ * (resp: n x k, row-major), labels[row] = the first maximum of resp[row]
+ * (int64, nullable), *log_prob_sum (device) = the sum of the rows' lse.     */
+int dkm_gm_estep_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *means, const double *precisions_chol,
+                     const double *log_det_w, int64_t k, int flags, void *ws,
+                     size_t ws_bytes, double *resp, int64_t *labels,
+                     double *log_prob_sum, void *stream);
+int dkm_gm_estep_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *means, const double *precisions_chol,
+                     const double *log_det_w, int64_t k, int flags, void *ws,
+                     size_t ws_bytes, double *resp, int64_t *labels,
+                     double *log_prob_sum, void *stream);
+/* Replaces _estimate_parameters_subset (:19-29) over all rows:
+ * out[0 .. k) = the column sums of resp, out[k .. k + k d) = resp^T X.     */
+int dkm_gm_mstep_sums_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                          const double *resp, int64_t k, void *ws,
+                          size_t ws_bytes, double *out, void *stream);
+int dkm_gm_mstep_sums_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                          const double *resp, int64_t k, void *ws,
+                          size_t ws_bytes, double *out, void *stream);
+/* Replaces _estimate_covariances_full (:103-117) over all rows: cov[c] (k x
+ * d x d) = sum_n resp[n][c] (x_n - means[c]) (x_n - means[c])^T, computed
+ * on and above the diagonal and mirrored.                                  */
+int dkm_gm_mstep_cov_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                         const double *resp, const double *means, int64_t k,
+                         void *ws, size_t ws_bytes, double *cov,
+                         void *stream);
+int dkm_gm_mstep_cov_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                         const double *resp, const double *means, int64_t k,
+                         void *ws, size_t ws_bytes, double *cov,
+                         void *stream);
+/* resp[i][c] = (labels[i] == c) ? 1 : 0 (_resp_subset, :770-776).          */
+int dkm_gm_onehot(const int32_t *labels, int64_t n, int64_t k, double *resp,
+                  void *stream);
 
 /* y[i] += x[i] (device, fp64): acc_new = acc_old + delta.                  */
 int dkm_add_f64(double *y, const double *x, int64_t n, void *stream);
