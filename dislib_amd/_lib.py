@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DKM_LIB", os.path.join(_HERE, "libdkm.so"))
 
 # constants mirrored from include/dkm.h
-ABI_VERSION = 8
+ABI_VERSION = 9
 MODE_AUTO, MODE_EXACT, MODE_SCREEN32, MODE_BF16X3, MODE_BF16 = 0, 1, 2, 3, 4
 MODE_MASK, MODE_NOHINT, MODE_B1, MODE_TRANSLATE = 0xff, 0x100, 0x200, 0x400
 IMAGE_NONE, IMAGE_SINGLE, IMAGE_SPLIT, IMAGE_SORTED, IMAGE_GEMM = 0, 1, 2, 3, 4
@@ -20,6 +20,7 @@ SUMS_F64, SUMS_F32, SUMS_RECIP = 0, 1, 2
 PREP_CSR = 1
 BOUNDS_INIT = 1
 GM_UPPER = 1
+DBSCAN_NOPRUNE = 1
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -152,6 +153,14 @@ SIGNATURES = {
                                        _f64, _i32, _p, _p, _sz, _p, _p, _p]),
     "dkm_radius_fill_f64": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64,
                                    _f64, _p, _p, _sz, _p, _p, _p]),
+    # DBSCAN: core flags, union-find over the core rows, labels
+    "dkm_dbscan_workspace_bytes": (_sz, [_i64, _i64]),
+    "dkm_dbscan_core_f64": (_i32, [_p, _i64, _i64, _i64, _f64, _i64, _i32,
+                                   _p, _sz, _p, _p]),
+    "dkm_dbscan_link_f64": (_i32, [_p, _i64, _i64, _i64, _f64, _i32, _p, _sz,
+                                   _p, _p, _p, _p, _p]),
+    "dkm_dbscan_finalize": (_i32, [_i64, _i64, _p, _sz, _p, _p, _p, _p, _p,
+                                   _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

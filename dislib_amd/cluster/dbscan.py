@@ -1,13 +1,70 @@
-"""DBSCAN's epsilon query on the GPU distance primitive.
+"""``DBSCAN`` -- drop-in for ``dislib.cluster.DBSCAN`` (dislib v0.2.0,
+``dislib/cluster/dbscan/base.py``) on a Dataset that is resident in HBM, and
+the epsilon query it is built on.
 
+``DBSCAN``
+----------
+Same constructor and private attributes as the reference (``base.py:68-82``,
+with its ``n_regions >= 1`` assertion) plus the keyword-only ``device``;
+``fit`` / ``fit_predict`` set the Subsets' labels and return ``None``;
+``n_clusters`` is the number of clusters found.
+
+The result is exact DBSCAN as the reference computes it with one region
+(``_compute_labels``, ``classes.py:162-191``):
+
+* two samples are neighbours when their ``_vec_matrix_euclid`` distance is
+  below ``eps`` -- the epsilon query's arithmetic and its ``dist < eps``
+  rule, decided as ``dkm_radius_count_f64`` decides it; a sample is its own
+  neighbour; ``eps <= 0`` gives no neighbours at all;
+* a sample with at least ``min_samples`` neighbours is a core point; two
+  core points within ``eps`` are in one component;
+* a non-core sample joins the component of its nearest core neighbour only,
+  ties going to the smallest (distance, Dataset row): it never links two
+  components, and with no core neighbour it is alone.  (The reference's
+  ``np.argsort`` leaves the order among exactly equal distances unpinned,
+  ``tests/test_neighbors_tie_rule.py``);
+* a component of fewer than ``min_samples`` members is noise (``-1``), even
+  when it holds a core point (``classes.py:187-189``: a lone core point
+  whose border points are all nearer to another core);
+* the other components are numbered 0, 1, ... by the smallest Dataset row
+  among their members.
+
+``n_regions``, ``dimensions``, ``arrange_data`` and ``max_samples`` are
+accepted and stored; they do not change the result.  In the reference they
+partition the work over tasks, and its multi-region result is this same
+clustering (up to the numbering) except in rare boundary cases, e.g. a sample
+that a neighbouring region, seeing only part of its neighbours, takes for
+non-core.  Here ``dimensions`` only picks the features of
+the cell ordering below.
+
+Where it runs.  The samples are ``dataset._device_data(device)``; fp32 and
+integer samples are widened to fp64 (as ``compute_neighbours`` widens them:
+numpy's ``vector - matrix`` of the reference stays in fp32 for fp32 samples,
+which is not reproduced).  Nothing n rows long comes to the host.  Torch
+orders the rows by grid cell of side ``eps`` (a stable sort of one int64 key,
+one gather); three calls of ``dkm_dbscan.hip`` then find the core points,
+union the core points within ``eps`` of each other (a lock-free union-find)
+and keep every non-core row's nearest core, and turn the forest into
+labels.  Memory is O(n): no neighbour list and nothing n x n exists, the
+distances are recomputed in each pass.  Labels leave as one int32 device
+tensor (``Dataset._attach_device_labels``) and materialise when a Subset's
+``labels`` are read.  Every result is a function of the input only, so labels
+are identical from run to run.
+
+Refusals.  A sparse Dataset and a ``torch.distributed`` world larger than 1
+raise ``NotImplementedError``; non-finite samples raise the ``ValueError`` of
+``compute_neighbours``' input check.  An empty Dataset and empty Subsets
+work (``n_clusters == 0``, empty labels).
+
+``compute_neighbours``
+----------------------
 Reference: ``_compute_neighbours`` of
 ``/root/reference/dislib/cluster/dbscan/classes.py:124-141`` -- for every
 sample of rows ``[begin_idx, end_idx)`` of the concatenated Subsets, the
 indices of all samples whose ``_vec_matrix_euclid`` distance (``:153-154``,
 numpy's ``sqrt(add.reduce((x - s)**2))`` in its pairwise order) is below
 ``epsilon``, ordered by distance, and whether there are at least
-``min_samples`` of them.  The rest of DBSCAN (grid regions, equivalence
-merging) is out of scope.
+``min_samples`` of them.
 
 Here the concatenated samples are uploaded once and ``dkm_radius_count_f64``
 / ``dkm_radius_fill_f64`` compute the same fp64 distances (bit-exact: the
@@ -27,8 +84,143 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from .._device import _is_torch, on, ptr, resolve, stream_ptr, torch
+from .._device import (_is_torch, on, preload, ptr, resolve, stream_ptr,
+                       torch)
 from .._device import assert_all_finite as _device_assert_finite
+
+# features in the ordering's cell key (63 bits shared among them)
+_KEY_DIMS = 16
+
+
+class DBSCAN:
+    """Exact DBSCAN on MI355X (see the module docstring).
+
+    Parameters match ``dislib.cluster.DBSCAN``; ``device`` is a keyword-only
+    extension.  fp32 and integer samples are widened to fp64.
+    """
+
+    def __init__(self, eps=0.5, min_samples=5, arrange_data=True, n_regions=1,
+                 dimensions=None, max_samples=None, *, device=None):
+        assert n_regions >= 1, \
+            "Number of regions must be greater or equal to 1."
+
+        self._eps = eps
+        self._min_samples = min_samples
+        self._n_regions = n_regions
+        self._dimensions_init = dimensions
+        self._dimensions = dimensions
+        self._arrange_data = arrange_data
+        self._subset_sizes = []
+        self._sorting = []
+        self._max_samples = max_samples
+        self._components = None
+        self._device = device
+        self._n_clusters = None      # device int32[1] of the last fit
+
+    def fit(self, dataset):
+        """Cluster ``dataset`` and set its Subsets' labels."""
+        from .. import _shard
+        if dataset.sparse:
+            raise NotImplementedError(
+                "DBSCAN takes dense samples (the epsilon query "
+                "compute_neighbours takes sparse Subsets)")
+        if _shard.active():
+            raise NotImplementedError(
+                "DBSCAN runs on one rank: a torch.distributed world larger "
+                "than 1 is not supported")
+        if self._dimensions_init is None:
+            self._dimensions = range(dataset.n_features)
+        _lib.lib()                          # no GPU / no libdkm: raise here
+        dd = dataset._device_data(self._device)
+        with on(dd.device):
+            preload(dd.device)
+            labels, n_clusters = _fit_device(
+                dd.X, float(self._eps), max(0, int(self._min_samples)),
+                list(self._dimensions))
+        self._n_clusters = n_clusters
+        self._components = None
+        dataset._attach_device_labels(labels)
+
+    def fit_predict(self, dataset):
+        """The same as :meth:`fit` (API standardisation, as the reference)."""
+        self.fit(dataset)
+
+    @property
+    def n_clusters(self):
+        if self._n_clusters is None:
+            raise AttributeError("n_clusters: call fit first")
+        if self._components is None:
+            self._components = list(range(int(self._n_clusters.item())))
+        return len(self._components)
+
+
+def _cell_order(X, eps, dims):
+    """The stable order of X's rows by grid cell of side ``eps`` over the
+    features ``dims`` (at most _KEY_DIMS of them, first = most significant),
+    as an int64 permutation; None when there is nothing to order by.  The
+    cell index of a feature is clamped so that all of them fit 63 bits."""
+    t = torch()
+    n, d = X.shape
+    dims = [int(c) for c in dims if 0 <= int(c) < d][:_KEY_DIMS]
+    if n < 2 or not dims or not (eps > 0) or eps == float("inf"):
+        return None
+    bits = 63 // len(dims)
+    top = float(2 ** min(bits, 52) - 1)
+    cols = X[:, dims]
+    cell = t.floor((cols - cols.min(dim=0).values) / eps).clamp_(0.0, top)
+    cell = cell.to(t.int64)
+    key = t.zeros(n, dtype=t.int64, device=X.device)
+    for c in range(len(dims)):
+        key = (key << bits) | cell[:, c]
+    return t.argsort(key, stable=True)
+
+
+def _fit_device(X, eps, min_samples, dims, flags=0):
+    """(labels int32[n], n_clusters int32[1]) on X's device for the (n, d)
+    device matrix ``X``; ``flags``: ``_lib.DBSCAN_NOPRUNE``."""
+    t = torch()
+    dev = X.device
+    n, d = X.shape
+    n_clusters = t.zeros(1, dtype=t.int32, device=dev)
+    labels = t.empty(n, dtype=t.int32, device=dev)
+    if n == 0:
+        return labels, n_clusters
+    X = X.to(t.float64)
+    if not bool(t.isfinite(X).all()):
+        if bool(t.isnan(X).any()):
+            raise ValueError("Input contains NaN.")
+        raise ValueError("Input contains infinity or a value too large for "
+                         "dtype('float64').")
+    so = _lib.lib()
+    perm = _cell_order(X, eps, dims)
+    if perm is None:
+        orig = t.arange(n, dtype=t.int32, device=dev)
+        Xs = X.contiguous()
+    else:
+        orig = perm.to(t.int32)
+        Xs = X.index_select(0, perm)
+    del X, perm
+    wsb = int(so.dkm_dbscan_workspace_bytes(n, d))
+    if wsb == 0:
+        raise ValueError("DBSCAN takes fewer than 2**31 - 64 samples, got %d"
+                         % n)
+    ws = t.empty(wsb, dtype=t.uint8, device=dev)
+    core = t.empty(n, dtype=t.int32, device=dev)
+    parent = t.empty(n, dtype=t.int32, device=dev)
+    attach = t.empty(n, dtype=t.int32, device=dev)
+    wp = ctypes.c_void_p(ws.data_ptr())
+    _lib.check(so.dkm_dbscan_core_f64(
+        ptr(Xs), n, d, Xs.stride(0), eps, min_samples, flags, wp, wsb,
+        ptr(core), stream_ptr()), "dkm_dbscan_core")
+    _lib.check(so.dkm_dbscan_link_f64(
+        ptr(Xs), n, d, Xs.stride(0), eps, flags, wp, wsb, ptr(core),
+        ptr(orig), ptr(parent), ptr(attach), stream_ptr()),
+        "dkm_dbscan_link")
+    _lib.check(so.dkm_dbscan_finalize(
+        n, min_samples, wp, wsb, ptr(core), ptr(orig), ptr(parent),
+        ptr(attach), ptr(labels), ptr(n_clusters), stream_ptr()),
+        "dkm_dbscan_finalize")
+    return labels, n_clusters
 
 
 def compute_neighbours(epsilon, min_samples, sparse, begin_idx, end_idx,

@@ -639,7 +639,8 @@ int dkm_preload(void) {
   bad += preload_dense() + preload_recheck() + preload_b2() +
          preload_sorted() + preload_cand() + preload_sparse() +
          preload_gemm() + preload_sums() + preload_neighbors() +
-         preload_ordered() + preload_scale() + preload_gm();
+         preload_ordered() + preload_scale() + preload_gm() +
+         preload_dbscan();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define DKM_ABI_VERSION 8
+#define DKM_ABI_VERSION 9
 
 /* error codes (besides hipError_t values passed through) */
 #define DKM_OK 0
@@ -684,6 +684,47 @@ int dkm_radius_fill_csr_f64(const int64_t *indptr, const int32_t *indices,
                             int64_t q0, int64_t nq, double eps, int out_f32,
                             const int64_t *offsets, void *ws, size_t ws_bytes,
                             int64_t *out_idx, double *out_dist, void *stream);
+
+/* ------------------------------------------------------------------------
+ * DBSCAN on the epsilon query's arithmetic, replacing
+ * _compute_labels (dislib/cluster/dbscan/classes.py:162-191) with one
+ * region: nothing n x n and no neighbour list, O(n) memory, the distances
+ * recomputed in each pass.  X is n x d fp64 (n <= INT32_MAX - 64) whose rows
+ * the caller has ordered so that neighbouring rows lie close together (by
+ * grid cell); orig_index[i] = the Dataset row of ordered row i, a
+ * permutation of 0 .. n - 1.  Any order gives the same result: tiles of 64
+ * consecutive rows carry a bounding box (first min(d, 16) features), and a
+ * tile pair whose boxes are more than eps (1 + 2^-40 on the square) apart
+ * is skipped.  The three calls share one workspace and run in this order.
+ * --------------------------------------------------------------------- */
+
+/* flags of dkm_dbscan_core_f64 / dkm_dbscan_link_f64: scan every tile pair */
+#define DKM_DBSCAN_NOPRUNE 1
+/* Workspace bytes (<= 64 n + 2^20; 0 for invalid sizes). */
+size_t dkm_dbscan_workspace_bytes(int64_t n, int64_t d);
+/* core_out[i] (int32) <- 1 when row i has at least min_samples rows j with
+ * dist(i, j) < eps (itself included), by dkm_radius_count_f64's predicate;
+ * eps <= 0: none. */
+int dkm_dbscan_core_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                        double eps, int64_t min_samples, int flags, void *ws,
+                        size_t ws_bytes, int32_t *core_out, void *stream);
+/* parent[n] <- a union-find forest over the ordered rows in which two core
+ * rows within eps share a root (non-core rows stay their own root);
+ * attach[i] <- for a non-core row the core row within eps of the smallest
+ * (distance, orig_index), or -1 (core rows: -1). */
+int dkm_dbscan_link_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                        double eps, int flags, void *ws, size_t ws_bytes,
+                        const int32_t *core, const int32_t *orig_index,
+                        int32_t *parent, int32_t *attach, void *stream);
+/* labels[orig_index[i]] (int32) <- the cluster of row i: components of the
+ * forest with their attached rows, those of fewer than min_samples rows
+ * dropped (-1), the others numbered from 0 by their smallest orig_index;
+ * *n_clusters (device int32) <- their count.  Path halving writes parent. */
+int dkm_dbscan_finalize(int64_t n, int64_t min_samples, void *ws,
+                        size_t ws_bytes, const int32_t *core,
+                        const int32_t *orig_index, int32_t *parent,
+                        const int32_t *attach, int32_t *labels,
+                        int32_t *n_clusters, void *stream);
 
 /* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`

@@ -1,0 +1,120 @@
+"""CPU tests of DBSCAN: the numpy statement of its semantics
+(tests/dbscan_ref.py) against the reference's own output
+(tests/golden/dbscan_ref.npz), and the estimator's host-side surface."""
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from tests import dbscan_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+G = np.load(os.path.join(ROOT, "tests", "golden", "dbscan_ref.npz"))
+CASES = sorted({k.split("__")[0] for k in G.files})
+
+
+@pytest.fixture(scope="module")
+def ref_results():
+    """dbscan_ref of every golden case, computed once."""
+    out = {}
+    for name in CASES:
+        _, eps, ms = G[name + "__meta"]
+        out[name] = ref.dbscan_ref(G[name + "__x"], float(eps), int(ms))
+    return out
+
+
+def test_golden_has_every_case():
+    assert CASES == ["blobs", "blobs_ms1", "d10", "doc", "steal"]
+    for name in CASES:
+        assert len(G[name + "__settings"]) == 5
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_ref_equals_reference_one_region(name, ref_results):
+    """Element for element, the numbering included."""
+    labels, ncl = ref_results[name]
+    assert np.array_equal(labels, G[name + "__labels_s0"])
+    assert ncl == int(G[name + "__ncl_s0"])
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_ref_equals_reference_other_settings(name, ref_results):
+    """After renumbering by first appearance."""
+    labels, ncl = ref_results[name]
+    for s in range(1, len(G[name + "__settings"])):
+        got = G["%s__labels_s%d" % (name, s)]
+        assert np.array_equal(ref.renumber(got), labels), s
+        assert ncl == int(G["%s__ncl_s%d" % (name, s)])
+
+
+def test_steal_case_core_point_is_noise(ref_results):
+    assert np.array_equal(ref_results["steal"][0], ref.STEAL_LABELS)
+    assert ref_results["steal"][0][0] == -1
+
+
+def test_import_and_constructor_attributes():
+    from dislib_amd.cluster import DBSCAN
+    est = DBSCAN()
+    assert (est._eps, est._min_samples, est._arrange_data, est._n_regions,
+            est._dimensions_init, est._dimensions, est._max_samples,
+            est._components) == (0.5, 5, True, 1, None, None, None, None)
+    assert est._subset_sizes == [] and est._sorting == []
+    est = DBSCAN(eps=3, min_samples=2, arrange_data=False, n_regions=4,
+                 dimensions=[1], max_samples=70, device="cuda:0")
+    assert (est._eps, est._min_samples, est._arrange_data, est._n_regions,
+            est._dimensions_init, est._dimensions, est._max_samples) == (
+                3, 2, False, 4, [1], [1], 70)
+    with pytest.raises(TypeError):
+        DBSCAN(0.5, 5, True, 1, None, None, "cuda:0")   # device: keyword-only
+
+
+def test_n_regions_assertion():
+    from dislib_amd.cluster import DBSCAN
+    with pytest.raises(AssertionError, match="Number of regions"):
+        DBSCAN(n_regions=0)
+
+
+def test_sparse_is_refused_before_any_gpu_use(monkeypatch):
+    from dislib_amd import _lib
+    from dislib_amd.cluster import DBSCAN
+    from dislib_amd.data import load_data
+
+    def boom(*a, **k):
+        raise AssertionError("the GPU library was touched")
+    monkeypatch.setattr(_lib, "lib", boom)
+    ds = load_data(sp.random(30, 5, density=0.3, format="csr",
+                             random_state=0), subset_size=10)
+    with pytest.raises(NotImplementedError, match="dense"):
+        DBSCAN().fit(ds)
+
+
+def test_distributed_world_is_refused(monkeypatch):
+    from dislib_amd import _lib, _shard
+    from dislib_amd.cluster import DBSCAN
+    from dislib_amd.data import load_data
+
+    def boom(*a, **k):
+        raise AssertionError("the GPU library was touched")
+    monkeypatch.setattr(_lib, "lib", boom)
+    monkeypatch.setattr(_shard, "world", lambda: (0, 2))
+    ds = load_data(np.zeros((6, 2)), subset_size=3)
+    with pytest.raises(NotImplementedError, match="one rank"):
+        DBSCAN().fit_predict(ds)
+
+
+def test_abi_constants_agree():
+    from dislib_amd import _lib
+    src = open(os.path.join(ROOT, "include", "dkm.h")).read()
+    consts = dict(re.findall(r"#define (DKM_\w+) (\d+)", src))
+    assert int(consts["DKM_ABI_VERSION"]) == _lib.ABI_VERSION == 9
+    assert int(consts["DKM_DBSCAN_NOPRUNE"]) == _lib.DBSCAN_NOPRUNE
+    so = _lib.load()
+    assert so.dkm_abi_version() == _lib.ABI_VERSION
+    for n in (1, 63, 64, 65, 2000, 20000, 10 ** 6, 10 ** 8):
+        for d in (1, 2, 130):
+            nb = so.dkm_dbscan_workspace_bytes(n, d)
+            assert 0 < nb <= 64 * n + 2 ** 20, (n, d, nb)
+    assert so.dkm_dbscan_workspace_bytes(-1, 2) == 0
+    assert so.dkm_dbscan_workspace_bytes(2 ** 31, 2) == 0
