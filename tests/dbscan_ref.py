@@ -8,6 +8,8 @@ give, and the pinned tie rule (distance, row) where the reference's
 tests/test_dbscan_host.py pins it to the goldens (the reference's own
 output) on the CPU; the GPU tests compare the kernels against it.
 """
+import collections
+
 import numpy as np
 
 
@@ -16,9 +18,16 @@ def _dist(x, i):
     return np.linalg.norm(x[i] - x, axis=1)
 
 
-def dbscan_ref(x, eps, min_samples):
-    """(labels int64[n], n_clusters) of the (n, d) samples ``x`` (widened to
-    fp64).  Two passes that recompute the distances: nothing n x n."""
+Parts = collections.namedtuple("Parts", "core attach comp labels n_clusters")
+
+
+def dbscan_parts(x, eps, min_samples):
+    """Every stage of the clustering of the (n, d) samples ``x`` (widened to
+    fp64): ``core`` bool[n]; ``attach`` int64[n], a non-core row's nearest
+    core neighbour or -1; ``comp`` int64[n], the smallest core row of a core
+    row's component, that of its ``attach`` for a border row, the row itself
+    for a lone one; ``labels`` int64[n] and ``n_clusters``.  Two passes that
+    recompute the distances: nothing n x n."""
     x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
     n = x.shape[0]
     core = np.zeros(n, dtype=bool)
@@ -33,7 +42,7 @@ def dbscan_ref(x, eps, min_samples):
             a = parent[a]
         return a
 
-    attach = np.full(n, -1)
+    attach = np.full(n, -1, dtype=np.int64)
     for i in range(n):
         dist = _dist(x, i)
         cand = np.flatnonzero((dist < eps) & core)
@@ -66,7 +75,13 @@ def dbscan_ref(x, eps, min_samples):
         if c not in number:
             number[c] = len(number)
         labels[i] = number[c]
-    return labels, len(number)
+    return Parts(core, attach, comp, labels, len(number))
+
+
+def dbscan_ref(x, eps, min_samples):
+    """(labels int64[n], n_clusters) of :func:`dbscan_parts`."""
+    p = dbscan_parts(x, eps, min_samples)
+    return p.labels, p.n_clusters
 
 
 def renumber(labels):
@@ -99,3 +114,140 @@ STEAL = np.array([[0, 0], [.9, 0], [-.9, 0], [0, .95], [1.5, 0], [2, 0],
                   [2.2, 0], [-1.5, 0], [-2, 0], [-2.2, 0], [0, 1.5], [0, 2],
                   [0, 2.2]], dtype=np.float64)
 STEAL_LABELS = np.array([-1, 0, 1, 2, 0, 0, 0, 1, 1, 1, 2, 2, 2])
+
+
+# Constructions whose labels are known without running dbscan_parts (it is
+# too slow beyond a few thousand rows).  tests/test_dbscan_host.py holds each
+# of them to dbscan_ref at a size where that is quick.
+
+def _by_smallest_row(group):
+    """(labels, n_clusters) of per-row group ids (-1 = noise): the groups
+    numbered by their smallest row."""
+    labels = renumber(group)
+    return labels, int(labels.max()) + 1 if labels.size else 0
+
+
+ISLANDS_EPS, ISLANDS_MS = 0.75, 4
+_SQUARE = np.array([[0, 0], [.5, 0], [0, .5], [.5, .5]])
+
+
+def islands(m, seed):
+    """(x, labels, n_clusters): ``m`` islands on a square lattice of pitch
+    4.0, island g the first 4 (g even) or 3 (g odd) corners of a square of
+    side 0.5, rows shuffled.  At eps = 0.75, min_samples = 4 a corner sees
+    the whole island (side 0.5, diagonal 0.707...) and nothing else, so every
+    4-island is a cluster of four core rows and every 3-island is noise.
+    Every coordinate is a multiple of 0.5: the squared distances are
+    exact."""
+    side = int(np.ceil(np.sqrt(m)))
+    pts, group = [], []
+    for g in range(m):
+        k = 4 if g % 2 == 0 else 3
+        pts.append(_SQUARE[:k] + [4.0 * (g % side), 4.0 * (g // side)])
+        group += [g if k == 4 else -1] * k
+    perm = np.random.default_rng(seed).permutation(len(group))
+    x = np.ascontiguousarray(np.concatenate(pts)[perm])
+    return (x,) + _by_smallest_row(np.array(group)[perm])
+
+
+CLIQUES_EPS, CLIQUES_MS = 1.5, 3
+
+
+def two_cliques(n_each, bridge, seed):
+    """(x, labels, n_clusters): ``n_each`` rows uniform in [0, 1]^2 and
+    ``n_each`` in [10, 11]^2, rows shuffled.  At eps = 1.5, min_samples = 3
+    each square is a clique of core rows (its diagonal is 1.414...) and the
+    squares are more than 12 apart: two clusters.  ``bridge`` adds rows 1.2
+    apart along y = 0.5 from (0.5, 0.5) to (10.1, 0.5) and on along x = 10.1
+    up to (10.1, 10.1).  Each has both chain neighbours at 1.2, so it is
+    core; the first is within 0.71 of all of the first square and the last
+    within 1.28 of all of the second: one cluster."""
+    rng = np.random.default_rng(seed)
+    a = rng.uniform(0.0, 1.0, (n_each, 2))
+    b = rng.uniform(10.0, 11.0, (n_each, 2))
+    group = [0] * n_each + [1] * n_each
+    parts = [a, b]
+    if bridge:
+        s = 0.5 + 1.2 * np.arange(9)
+        chain = np.concatenate([np.stack([s, np.full(9, 0.5)], -1),
+                                np.stack([np.full(8, s[-1]), s[1:]], -1)])
+        parts.append(chain)
+        group = [0] * (2 * n_each + len(chain))
+    perm = rng.permutation(len(group))
+    x = np.ascontiguousarray(np.concatenate(parts)[perm])
+    return (x,) + _by_smallest_row(np.array(group)[perm])
+
+
+TIE_VARIANTS = ("one_tile", "two_partitions", "three_way")
+Tie = collections.namedtuple(
+    "Tie", "x order b cores labels n_clusters eps min_samples")
+
+
+def tie_case(variant, fill=True, seed=0):
+    """Integer-coordinate samples in which the non-core row ``b`` = (0, 0)
+    is at distance exactly 2 from one core row of each of two (three for
+    ``"three_way"``) clusters and from no other row.
+
+    Cluster a lies along the unit vector u_a (east, west, north), v_a
+    perpendicular to it: the tied core 2 u, then 3 u, 4 u, 3 u + v, 3 u - v.
+    At eps = 2.2 each of the five sees the other four (distances 1, 1.41, 2),
+    no row of another arm (2.83 at the least), and only 2 u sees ``b``
+    (3 u +- v is 3.16 from it).  So with min_samples = 4 (5 for
+    ``"three_way"``, where ``b`` has four neighbours) all five are core,
+    ``b`` is not, and ``b`` joins the tied core with the smallest row.
+    ``fill`` adds 150 unit squares on a lattice of pitch 10 from (100, 100)
+    on: n > 600, two partitions of five tiles.  Each is a cluster at
+    min_samples = 4 and noise at 5.
+
+    ``x`` is in Dataset row order.  ``order`` is a row order for the kernels
+    (ordered row i is ``x[order[i]]``, i.e. an ``orig_index``) that puts the
+    tied cores where the variant says, the one with the smaller Dataset row
+    always at the larger position:
+
+    * ``"one_tile"``: positions 40 and 10 of the first tile;
+    * ``"two_partitions"``: the last tile (second partition) and the first;
+    * ``"three_way"``: the last tile, a tile between, the first tile.
+
+    ``cores`` are the tied cores' Dataset rows, ascending, so ``cores[0]``
+    wins.  ``labels`` / ``n_clusters`` follow from the construction."""
+    k = 3 if variant == "three_way" else 2
+    ms = 5 if k == 3 else 4
+    pts, group = [[0, 0]], [0]                    # b goes with arm 0
+    for a, (ux, uy) in enumerate([(1, 0), (-1, 0), (0, 1)][:k]):
+        vx, vy = -uy, ux
+        pts += [[2 * ux, 2 * uy], [3 * ux, 3 * uy], [4 * ux, 4 * uy],
+                [3 * ux + vx, 3 * uy + vy], [3 * ux - vx, 3 * uy - vy]]
+        group += [a] * 5
+    tied = [1 + 5 * a for a in range(k)]          # rows of pts
+    if fill:
+        unit = 2 * _SQUARE
+        for g in range(150):
+            pts += list(unit + [100 + 10 * (g % 16), 100 + 10 * (g // 16)])
+            group += [k + g if ms == 4 else -1] * 4
+    pts = np.array(pts, dtype=np.float64)
+    group = np.array(group)
+    n = len(pts)
+    if not fill:
+        where = {"one_tile": [n - 1, 0], "three_way": [n - 1, n // 2, 0]}
+    else:
+        where = {"one_tile": [40, 10], "two_partitions": [n - 3, 5],
+                 "three_way": [n - 3, 330, 10]}
+    where = where[variant]
+    rng = np.random.default_rng(seed)
+    # rows: pts in kernel order, the tied cores moved to their positions
+    slot = rng.permutation(n)
+    for t, w in zip(tied, where):
+        i = int(np.flatnonzero(slot == t)[0])
+        slot[i], slot[w] = slot[w], slot[i]
+    # Dataset rows: arm 0's core gets the smallest of the tied cores' rows
+    order = rng.permutation(n)
+    vals = np.sort(order[where])
+    order[where] = vals
+    x = np.empty_like(pts)
+    x[order] = pts[slot]
+    g_ds = np.empty_like(group)
+    g_ds[order] = group[slot]
+    labels, ncl = _by_smallest_row(g_ds)
+    b = int(order[np.flatnonzero(slot == 0)[0]])
+    return Tie(np.ascontiguousarray(x), order.astype(np.int64), b,
+               [int(v) for v in vals], labels, ncl, 2.2, ms)

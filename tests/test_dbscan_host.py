@@ -54,6 +54,79 @@ def test_steal_case_core_point_is_noise(ref_results):
     assert ref_results["steal"][0][0] == -1
 
 
+def test_parts_are_consistent(ref_results):
+    """dbscan_ref is dbscan_parts' labels; attach and comp mean what the GPU
+    tests take them to mean."""
+    for name in CASES:
+        _, eps, ms = G[name + "__meta"]
+        p = ref.dbscan_parts(G[name + "__x"], float(eps), int(ms))
+        assert np.array_equal(p.labels, ref_results[name][0])
+        assert p.n_clusters == ref_results[name][1]
+        assert p.core.dtype == bool and (p.attach[p.core] == -1).all()
+        has = p.attach >= 0
+        assert p.core[p.attach[has]].all()
+        assert np.array_equal(p.comp[has], p.comp[p.attach[has]])
+        assert (p.comp[p.core] <= np.flatnonzero(p.core)).all()
+        lone = ~p.core & ~has
+        assert np.array_equal(p.comp[lone], np.flatnonzero(lone))
+
+
+def test_islands_labels_are_the_reference():
+    x, labels, ncl = ref.islands(300, 1)
+    assert x.shape == (1050, 2) and ncl == 150
+    assert np.array_equal(x, np.round(x * 2) / 2)
+    want, wncl = ref.dbscan_ref(x, ref.ISLANDS_EPS, ref.ISLANDS_MS)
+    assert np.array_equal(labels, want) and ncl == wncl
+    assert np.count_nonzero(labels == -1) == 450
+
+
+@pytest.mark.parametrize("bridge", [True, False])
+def test_two_cliques_labels_are_the_reference(bridge):
+    x, labels, ncl = ref.two_cliques(200, bridge, 2)
+    assert len(x) == 400 + (17 if bridge else 0)
+    assert ncl == (1 if bridge else 2) and (labels >= 0).all()
+    p = ref.dbscan_parts(x, ref.CLIQUES_EPS, ref.CLIQUES_MS)
+    assert np.array_equal(labels, p.labels) and ncl == p.n_clusters
+    assert p.core.all()
+
+
+@pytest.mark.parametrize("variant,fill", [
+    (v, True) for v in ref.TIE_VARIANTS] + [
+    ("one_tile", False), ("three_way", False)])
+def test_tie_case(variant, fill):
+    t = ref.tie_case(variant, fill=fill)
+    n = len(t.x)
+    assert np.array_equal(t.x, np.round(t.x))
+    assert np.array_equal(np.sort(t.order), np.arange(n))
+    p = ref.dbscan_parts(t.x, t.eps, t.min_samples)
+    assert np.array_equal(t.labels, p.labels) and t.n_clusters == p.n_clusters
+    assert not p.core[t.b] and p.labels[t.b] >= 0
+    assert len(t.cores) == (3 if variant == "three_way" else 2)
+    assert t.cores == sorted(t.cores) and p.core[t.cores].all()
+    # the tie is exact, the tied cores are b's only core neighbours and they
+    # are cores of different clusters; the smallest row wins
+    dist = np.linalg.norm(t.x[t.b] - t.x, axis=1)
+    assert dist.dtype == np.float64
+    for c in t.cores:
+        assert dist[c] == dist[t.cores[0]] == 2.0
+    near = np.flatnonzero((dist < t.eps) & p.core)
+    assert sorted(near) == t.cores
+    assert len({int(p.comp[c]) for c in t.cores}) == len(t.cores)
+    assert p.attach[t.b] == t.cores[0]
+    assert p.labels[t.b] == p.labels[t.cores[0]]
+    # where the kernels' row order puts them: the smaller row further back
+    pos = [int(np.flatnonzero(t.order == c)[0]) for c in t.cores]
+    assert pos == sorted(pos, reverse=True)
+    if fill:
+        assert n >= 600
+        tiles = [q // 64 for q in pos]
+        if variant == "one_tile":
+            assert tiles == [0, 0]
+        else:                       # 10 tiles, two partitions of 5
+            assert tiles[0] == 9 and tiles[-1] == 0
+            assert variant == "two_partitions" or tiles[1] == 5
+
+
 def test_import_and_constructor_attributes():
     from dislib_amd.cluster import DBSCAN
     est = DBSCAN()
