@@ -17,11 +17,13 @@ from dislib_amd._shard import shard_dataset, shard_range  # noqa: E402,F401
 
 def install_as_dislib():
     """Alias ``dislib``, ``dislib.cluster``, ``dislib.data``,
-    ``dislib.neighbors`` and ``dislib.preprocessing`` to this package (the
-    k-means path, its data containers, the kNN reuse of its distance
-    primitive and the StandardScaler)."""
+    ``dislib.neighbors``, ``dislib.preprocessing`` and
+    ``dislib.recommendation`` to this package (the k-means path, its data
+    containers, the kNN reuse of its distance primitive, the StandardScaler
+    and ALS)."""
     import types
-    from dislib_amd import cluster, data, neighbors, preprocessing
+    from dislib_amd import (cluster, data, neighbors, preprocessing,
+                            recommendation)
     pkg = types.ModuleType("dislib")
     pkg.__path__ = []
     pkg.name = "dislib"
@@ -29,8 +31,10 @@ def install_as_dislib():
     pkg.data = data
     pkg.neighbors = neighbors
     pkg.preprocessing = preprocessing
+    pkg.recommendation = recommendation
     sys.modules["dislib"] = pkg
     sys.modules["dislib.preprocessing"] = preprocessing
+    sys.modules["dislib.recommendation"] = recommendation
     sys.modules["dislib.neighbors"] = neighbors
     sys.modules["dislib.cluster"] = cluster
     sys.modules["dislib.data"] = data

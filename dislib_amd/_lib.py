@@ -21,6 +21,7 @@ PREP_CSR = 1
 BOUNDS_INIT = 1
 GM_UPPER = 1
 DBSCAN_NOPRUNE = 1
+ALS_MAX_NF, ALS_CHUNK = 128, 16
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -161,6 +162,15 @@ SIGNATURES = {
                                    _p, _p, _p, _p, _p]),
     "dkm_dbscan_finalize": (_i32, [_i64, _i64, _p, _sz, _p, _p, _p, _p, _p,
                                    _p, _p]),
+    # ALS: one half-step, the squared error, the item means
+    "dkm_als_workspace_bytes": (_sz, [_i64, _i64]),
+    "dkm_als_update_f64": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64,
+                                  _f64, _p, _p]),
+    "dkm_als_update_f32": (_i32, [_p, _p, _p, _i64, _p, _i64, _i64, _i64,
+                                  _f64, _p, _p]),
+    "dkm_als_sse": (_i32, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64,
+                           _i64, _p, _sz, _p, _p]),
+    "dkm_als_row_means": (_i32, [_p, _p, _i64, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

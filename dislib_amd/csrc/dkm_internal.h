@@ -34,6 +34,7 @@ int preload_ordered();
 int preload_scale();
 int preload_gm();
 int preload_dbscan();
+int preload_als();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -62,6 +63,7 @@ int tu_flags_ordered();
 int tu_flags_scale();
 int tu_flags_gm();
 int tu_flags_dbscan();
+int tu_flags_als();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

@@ -49,6 +49,15 @@ def _freeze(x):
                 a.setflags(write=False)
 
 
+def _transpose_bounds(n_cols, n_subsets):
+    """The column ranges ``[(begin, end), ...]`` of the reference's
+    ``_get_split_i`` (classes.py:396-413) for every group."""
+    n_cols, n_subsets = int(n_cols), int(n_subsets)
+    stride = n_cols // n_subsets if n_subsets > 0 else 0
+    return [(i * stride, n_cols if i == n_subsets - 1 else (i + 1) * stride)
+            for i in range(n_subsets)]
+
+
 class _DeviceLabels:
     """Labels of a whole Dataset, resident on the device (int32)."""
 
@@ -181,6 +190,25 @@ class Dataset(object):
         self._subsets.extend(subsets)
         self._sizes.extend([None] * len(subsets))
         self._reset_attributes()
+
+    def transpose(self, n_subsets=None):
+        """The transposed Dataset, divided by rows into ``n_subsets`` Subsets
+        (default: as many as this one has).  Reference ``Dataset.transpose``
+        with its split rule (classes.py:80-110, 396-426): group ``i`` takes
+        columns ``[i * stride, (i + 1) * stride)`` with ``stride = n_cols //
+        n_subsets``, the last group everything that remains.  Host samples
+        only; the result shares nothing with this Dataset."""
+        if n_subsets is None:
+            n_subsets = len(self._subsets)
+        stack_f = sp.vstack if self._sparse else np.vstack
+        subsets_t = []
+        for a, b in _transpose_bounds(self.n_features, n_subsets):
+            cols = [s.samples[:, a:b] for s in self._subsets]
+            subsets_t.append(Subset(samples=stack_f(cols).transpose()))
+        n_rows = int(np.sum(self.subsets_sizes()))
+        dataset_t = Dataset(n_features=n_rows, sparse=self._sparse)
+        dataset_t.extend(subsets_t)
+        return dataset_t
 
     def subset_size(self, index):
         if self._sizes[index] is None:

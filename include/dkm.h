@@ -727,6 +727,54 @@ int dkm_dbscan_finalize(int64_t n, int64_t min_samples, void *ws,
                         int32_t *n_clusters, void *stream);
 
 /* ------------------------------------------------------------------------
+ * ALS, replacing _update_chunk and _get_rmse of
+ * dislib/recommendation/als/base.py:225-253.  The ratings are a CSR matrix
+ * (indptr[n_rows+1] int64, indices int32, data fp64); stored entries equal
+ * to 0 are skipped everywhere but in the row means, as sparse.find skips
+ * them.  An entry whose column is outside the factor matrix is skipped too.
+ * Every sum has a fixed order: results are identical from run to run.
+ * --------------------------------------------------------------------- */
+
+/* Most latent factors (A and the gather tile share the 160 KiB of LDS). */
+#define DKM_ALS_MAX_NF 128
+/* Factor rows gathered per pass of dkm_als_update_* (tests walk its edges). */
+#define DKM_ALS_CHUNK 16
+/* Workspace bytes of dkm_als_sse over n_rows rows; 0 for invalid sizes
+ * (n_rows < 0 or > INT32_MAX, n_f outside 1 .. DKM_ALS_MAX_NF).  Host-only. */
+size_t dkm_als_workspace_bytes(int64_t n_rows, int64_t n_f);
+/* One half-step.  For row i with non-zero entries at columns idx (n_c of
+ * them, values r): Y[i] (fp32, n_rows x n_f, contiguous) <- the solution y
+ * of (X[idx]^T X[idx] + lambda n_c I) y = X[idx]^T r, with the Gram matrix
+ * accumulated, factored (Cholesky) and solved in fp64 and y rounded to fp32
+ * on store; zeros for a row without a non-zero entry.  X is m x n_f with
+ * row stride ldx, 1 <= n_f <= DKM_ALS_MAX_NF. */
+int dkm_als_update_f64(const int64_t *indptr, const int32_t *indices,
+                       const double *data, int64_t n_rows, const double *X,
+                       int64_t m, int64_t n_f, int64_t ldx, double lambda,
+                       float *Y, void *stream);
+int dkm_als_update_f32(const int64_t *indptr, const int32_t *indices,
+                       const double *data, int64_t n_rows, const float *X,
+                       int64_t m, int64_t n_f, int64_t ldx, double lambda,
+                       float *Y, void *stream);
+/* out[0] (device fp64) <- the sum over the non-zero entries (row, col, r) of
+ * CSR rows row_begin <= row < row_end of (r - u . i)^2 with u =
+ * users[row - row_begin + user_offset] and i = items[col] (both fp32,
+ * contiguous rows of n_f; the dot and the sum in fp64); out[1] <- their
+ * count.  user_offset = row_begin indexes users by the CSR row; 0 indexes
+ * them by the row's number inside the range, which is how the reference
+ * scores the Subsets of its transposed Dataset (base.py:123-126).  Needs
+ * row_end - row_begin + user_offset <= n_users. */
+int dkm_als_sse(const int64_t *indptr, const int32_t *indices,
+                const double *data, int64_t row_begin, int64_t row_end,
+                int64_t user_offset, const float *users, int64_t n_users,
+                const float *items, int64_t n_items, int64_t n_f, void *ws,
+                size_t ws_bytes, double *out, void *stream);
+/* out[i] (fp64) <- the mean of row i's stored entries, zeros included; NaN
+ * for a row that stores none (np.mean(row.data), base.py:162). */
+int dkm_als_row_means(const int64_t *indptr, const double *data,
+                      int64_t n_rows, double *out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
