@@ -133,6 +133,7 @@ SIGNATURES = {
                                         _p, _sz, _p, _p, _p]),
     "dkm_predict_csr_f64": (_i32, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _sz,
                                    _p, _p]),
+    "dkm_csr_slices": (_i32, [_i64, _i64, ctypes.POINTER(_i64)]),
     "dkm_make_blobs_f64": (_i32, [_p, _i64, _i64, _i64, _i64, _u64, _f64,
                                   _f64, _p, _p]),
     "dkm_screen_stats": (_i32, [_p, ctypes.POINTER(_i64), _p]),

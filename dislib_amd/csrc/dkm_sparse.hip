@@ -630,6 +630,12 @@ int dkm_predict_csr_f64(const int64_t *indptr, const int32_t *indices,
                  nullptr, OP_PREDICT, stream, "dkm_predict_csr_f64");
 }
 
+int dkm_csr_slices(int64_t k, int64_t d, int64_t *width) {
+  if (k < 1 || d < 1) return 0;
+  if (width) *width = csr_slice_width(k, d);
+  return csr_slices(k, d);
+}
+
 }  // extern "C"
 
 // Code-object preload (dkm_preload): the runtime loads this file's kernels

@@ -541,6 +541,12 @@ int dkm_predict_csr_f64(const int64_t *indptr, const int32_t *indices,
                         const double *data, int64_t n, int64_t d,
                         const double *C, int64_t k, const void *ws,
                         size_t ws_bytes, int32_t *labels, void *stream);
+/* Host query: the number of slices (1, 2, 4 or 8) the CSR screen cuts its
+ * bf16 C^T of (k, d) into and, when `width` is not NULL, the centres per
+ * slice (a multiple of 64; slice s holds centres [s width, (s + 1) width)
+ * below k, so the last slices may hold fewer or none).  0 for k < 1 or
+ * d < 1.                                                                   */
+int dkm_csr_slices(int64_t k, int64_t d, int64_t *width);
 
 /* ------------------------------------------------------------------------
  * Multi-GPU: the one collective of a Lloyd iteration (SURVEY.md section

@@ -234,15 +234,17 @@ def _ragged_csr(rng, n, d, per_row):
 
 
 @pytest.mark.parametrize("n,d,k,per_row,seed,nq", [
+    # every shape here is ONE slice (a bf16 C^T below 16 MiB); the sliced
+    # tables are in test_gpu_csr_kernels.py
     (2000, 400, 200, 90, 0, 0),     # > 16 stored entries: several chunks
-    (3000, 5000, 256, 10, 1, 0),    # 10 MB C^T: 4 centre slices
-    (1500, 300, 60, 5, 2, 0),       # one slice, one pass
-    (1000, 200, 600, 20, 3, 0),     # one slice, two 32-centre passes/walk
-    (2500, 10000, 256, 10, 4, 0),   # C5's d and k: 8 slices of 32 centres
-    (2100, 4000, 333, 8, 5, 0),     # odd k: uneven last slice, padded C^T
-    (1800, 10000, 256, 6, 6, 512)])  # small workspace tail: 50 sample chunks
+    (3000, 5000, 256, 10, 1, 0),    # 2.6 MB C^T: one walk of 4 passes
+    (1500, 300, 60, 5, 2, 0),       # one pass of 64 centres
+    (1000, 200, 600, 20, 3, 0),     # 10 passes: three walks of 4
+    (2500, 10000, 256, 10, 4, 0),   # C5's d and k: a 5.1 MB C^T
+    (2100, 4000, 333, 8, 5, 0),     # odd k: 6 passes, padded C^T
+    (1800, 10000, 256, 6, 6, 512)])  # small workspace tail: 256-row chunks
 def test_csr_predict_and_partial_sum_vs_oracle(n, d, k, per_row, seed, nq):
-    """CSR assignment (k_csr_slice + k_csr_merge) against the oracle's
+    """CSR assignment (k_csr_screen + k_csr_merge) against the oracle's
     sklearn-order arithmetic on ragged rows: labels bit-exact, sums 1e-12;
     then the incremental form from a perturbed previous assignment."""
     from dislib_amd import _device, _lib
