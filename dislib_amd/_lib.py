@@ -142,6 +142,8 @@ SIGNATURES = {
                                 _p]),
     # distance-primitive reuse (kNN, DBSCAN epsilon query)
     "dkm_knn_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dkm_knn_plan": (_i32, [_i64, _i64, _i64, ctypes.POINTER(_i64),
+                            ctypes.POINTER(_i32)]),
     "dkm_knn_f64": (_i32, [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p,
                            _sz, _p, _p, _p]),
     "dkm_knn_csr_f64": (_i32, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i64,

@@ -1002,6 +1002,21 @@ size_t dkm_knn_workspace_bytes(int64_t nq, int64_t nx, int64_t kn) {
   return kb_applies(kn) ? std::max(passes, kb_bytes(nq, nx, kn)) : passes;
 }
 
+int dkm_knn_plan(int64_t nq, int64_t nx, int64_t kn, int64_t *plen,
+                 int32_t *parts) {
+  if (nq < 1 || nx < 1 || nx > INT32_MAX || kn < 1 || kn > nx) return 0;
+  const bool kb = kb_applies(kn);
+  int64_t pl;
+  int P;
+  if (kb)
+    kb_grid(nq, nx, kn, &pl, &P);
+  else
+    knn_grid(nq, nx, &pl, &P);
+  if (plen) *plen = pl;
+  if (parts) *parts = P;
+  return kb ? 2 : 1;
+}
+
 int dkm_knn_f64(const double *Q, int64_t nq, int64_t ldq, const double *X,
                 int64_t nx, int64_t ldx, int64_t d, int64_t kn, void *ws,
                 size_t ws_bytes, double *out_dist, int64_t *out_idx,

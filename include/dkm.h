@@ -623,6 +623,17 @@ int dkm_build_flags(void);
 
 /* Workspace bytes of dkm_knn_f64 (0 for invalid sizes). */
 size_t dkm_knn_workspace_bytes(int64_t nq, int64_t nx, int64_t kn);
+/* Host query (launches nothing): how dkm_knn_f64 / dkm_knn_csr_f64 cut the
+ * fit rows for (nq, nx, kn).  Returns 1 when the call runs passes of <= 32
+ * columns (kn <= 32 or kn > 2048), 2 when it takes the two-scan path
+ * (32 < kn <= 2048), and writes, where not NULL, the rows per partition and
+ * the number of partitions of that path (partition p = rows [p plen,
+ * (p + 1) plen) below nx).  A two-scan call whose candidate list outgrows
+ * 4096 entries for some query reruns in the passes' partitions, which do not
+ * depend on kn (ask with kn = 1).  0 for nq < 1, nx < 1, nx > INT32_MAX or
+ * kn outside [1, nx].                                                      */
+int dkm_knn_plan(int64_t nq, int64_t nx, int64_t kn, int64_t *plen,
+                 int32_t *parts);
 /* For each query row of Q (nq x d): the kn (1..32, <= nx) rows of X
  * (nx x d) nearest by dist = sqrt(r), r = sum_t (q_t - x_t)^2 summed
  * sequentially from t = 0 (sklearn KD-tree EuclideanDistance.rdist, the

@@ -61,9 +61,9 @@ def test_kneighbors_reference_golden(name):
     (700, 3000, 70, 8, 2),       # d > 64: query read from memory
     (129, 300, 64, 1, 3),        # ragged last wave, one neighbour
     (64, 257, 9, 17, 4),         # k between templates (K = 32 slots)
-    (500, 3000, 5, 33, 5),       # n_neighbors > 32: a second pass of one
-    (300, 2000, 12, 100, 6),     # four passes, the last of 4 columns
-    (200, 700, 70, 64, 7),       # exactly two full passes, d > 64
+    (500, 3000, 5, 33, 5),       # n_neighbors > 32: the two-scan path
+    (300, 2000, 12, 100, 6),     # two scans again (passes: kn > 2048)
+    (200, 700, 70, 64, 7),       # two scans, d > 64 (query from memory)
     (300, 20000, 5, 1000, 8),    # the two-scan path (32 < kn <= 2048)
     (130, 6144, 70, 2048, 9),    # its largest kn, d > 64
     (64, 1200, 3, 1200, 10),     # kn = nx: every row
