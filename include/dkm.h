@@ -748,7 +748,13 @@ int dkm_dbscan_finalize(int64_t n, int64_t min_samples, void *ws,
  * dislib/recommendation/als/base.py:225-253.  The ratings are a CSR matrix
  * (indptr[n_rows+1] int64, indices int32, data fp64); stored entries equal
  * to 0 are skipped everywhere but in the row means, as sparse.find skips
- * them.  An entry whose column is outside the factor matrix is skipped too.
+ * them.  An entry whose column is outside the factor matrix (index < 0, or
+ * >= m in dkm_als_update_*, >= n_items in dkm_als_sse) is skipped too: it
+ * adds nothing to the Gram matrix, to v, to n_c or to the squared error and
+ * its count, and no factor row is read for it; a row with such entries only
+ * is a row without entries.  Factor rows that no counted entry names are
+ * never read.  Column indices need not be sorted, and a column stored twice
+ * in a row counts as two entries.
  * Every sum has a fixed order: results are identical from run to run.
  * --------------------------------------------------------------------- */
 

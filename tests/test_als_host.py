@@ -202,3 +202,149 @@ def test_abi_constants_agree():
     assert so.dkm_als_workspace_bytes(0, 1) > 0
     for bad in ((-1, 8), (2 ** 31, 8), (10, 0), (10, 129)):
         assert so.dkm_als_workspace_bytes(*bad) == 0
+
+
+# --------------------------------------------------------------------------
+# The longdouble yardstick of the kernel tests (tests/als_ref.py, 2nd half)
+# --------------------------------------------------------------------------
+LD, U = ref.LD, ref.U
+
+
+def test_longdouble_is_wider_than_fp64():
+    assert np.finfo(LD).eps <= 2.0 ** -63
+
+
+@pytest.mark.parametrize("n", [1, 2, 17, 128])
+def test_solve_ld_agrees_with_fp64_solve_when_well_conditioned(n):
+    """Within 8 n cond u of np.linalg.solve, whose own forward error that
+    is; solve_ld's is 2^-11 of it."""
+    rng = np.random.default_rng(n)
+    for trial in range(3):
+        b = rng.uniform(-1, 1, (n + 3 + trial, n))
+        a = b.T.dot(b) + 0.5 * np.eye(n)
+        v = rng.uniform(-5, 5, n)
+        y, y64 = ref.solve_ld(a, v), np.linalg.solve(a, v)
+        assert y.dtype == LD
+        bound = 8 * n * np.linalg.cond(a) * U * np.abs(y64).max()
+        assert (np.abs((y - y64).astype(np.float64)) <= bound).all()
+
+
+@pytest.mark.parametrize("n_f", ref.COND_NF)
+def test_conditioning_inputs_keep_the_bound_a_check(n_f):
+    """The small-lambda family: n_c = 1, 2, n_f - 1, n_f, n_f + 1, the
+    bound's conditioning term at most 2^-12 for every row, and solve_ld's
+    residual below the fp64 solve's."""
+    for dtype in (np.float64, np.float32):
+        m, x = ref.conditioning_case(n_f, dtype)
+        assert x.dtype == dtype and x.min() < -0.9 and x.max() > 0.9
+        assert list(np.diff(m.indptr)) == [1, 2, n_f - 1, n_f, n_f + 1]
+        rows = ref.update_rows(m, x, ref.COND_LAMBDA)
+        worst = 0.0
+        for i, (y, cond) in enumerate(rows):
+            assert 8 * n_f * cond * U <= 2.0 ** -12, (i, cond)
+            assert cond <= 1 + n_f / ref.COND_LAMBDA
+            worst = max(worst, cond)
+            idx, r = ref.used_entries(m, i, x.shape[0])
+            a, v = ref.normal_equations(idx, r, x, ref.COND_LAMBDA, LD)
+            a64, v64 = ref.normal_equations(idx, r, x, ref.COND_LAMBDA)
+            y64 = np.linalg.solve(a64, v64)
+            res = np.abs(a.dot(y) - v).max()
+            res64 = np.abs(a.dot(y64.astype(LD)) - v).max()
+            assert np.isfinite(float(res64)) and res <= res64, (i, res, res64)
+        assert worst > 1e6                   # ... and it is ill-conditioned
+        print("n_f %d %s: largest cond %.3g" % (n_f, np.dtype(dtype).name,
+                                                worst))
+
+
+def test_update_rows_entry_rule():
+    """Used iff data != 0 and 0 <= index < n_cols; duplicates stay apart in
+    the Gram sum and in n_c; no entry gives zeros."""
+    x = np.random.default_rng(3).uniform(-1, 1, (6, 4))
+    m = ref.Csr.from_rows([([1, 7, -1, 3], [2.0, 9.0, 9.0, 0.0]),   # one
+                           ([5, 6, -2], [1.0, 2.0, 3.0]),           # none
+                           ([], []),
+                           ([2, 2, 4], [1.5, -0.5, 3.0]),           # twice
+                           ([4, 2, 2], [3.0, -0.5, 1.5])], 5)
+    rows = ref.update_rows(m, x, 0.1, 5)
+    a = np.outer(x[1], x[1]) + 0.1 * np.eye(4)
+    assert np.allclose(rows[0][0].astype(float), np.linalg.solve(a, 2 * x[1]),
+                       rtol=1e-12, atol=0)
+    for i in (1, 2):
+        assert np.array_equal(rows[i][0], np.zeros(4)) and rows[i][1] == 0.0
+    a = 2 * np.outer(x[2], x[2]) + np.outer(x[4], x[4]) + 0.3 * np.eye(4)
+    want = np.linalg.solve(a, x[2] + 3 * x[4])
+    assert np.allclose(rows[3][0].astype(float), want, rtol=1e-12, atol=0)
+    assert np.allclose(rows[4][0].astype(float), want, rtol=1e-12, atol=0)
+    summed = np.linalg.solve(a - np.outer(x[2], x[2]) - 0.1 * np.eye(4),
+                             x[2] + 3 * x[4])
+    assert not np.allclose(want, summed, rtol=1e-3)
+    # with the bound at x.shape[0] = 6, column 5 of row 1 comes in
+    assert ref.update_rows(m, x, 0.1)[1][1] > 0
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_longdouble_restatement_reproduces_update(name, ref_results):
+    """update_rows against als_ref.update on the goldens' inputs (the last
+    items half-step of the fit, and the first users half-step from the fp64
+    initial items with their NaN means): within the fp32 store and the fp64
+    solve's own forward bound."""
+    r, sub, test, args = _inputs(name)
+    res = ref_results[name]
+    r_i = sp.csr_matrix(r, dtype=np.float64)
+    r_u = sp.csr_matrix(r_i.T)
+    r_u.sort_indices()
+    n_f, lam, seed = args[0], args[1], args[5]
+    for m, x in ((r_i, res.users), (r_u, ref.initial_items(r_i, n_f, seed))):
+        y32 = ref.update(m, x, lam)
+        if m is r_i:
+            assert np.array_equal(y32, res.items)
+        rows = ref.update_rows(m, x, lam)
+        assert len(rows) == m.shape[0]
+        for i, (y, cond) in enumerate(rows):
+            err = np.abs((y32[i].astype(LD) - y).astype(np.float64))
+            assert (err <= ref.update_bound(y, cond, n_f)).all(), i
+        # the fp64 flavour is als_ref.update before the store
+        rows64 = ref.update_rows(m, x, lam, dtype=np.float64)
+        assert np.array_equal(
+            np.array([y for y, _ in rows64]).astype(np.float32), y32)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_longdouble_restatement_reproduces_sse(name, ref_results):
+    """sse_ld against als_ref.sse on the goldens: the count exactly, the sum
+    within the derived bound at numpy's depth (the square's own rounding,
+    any order inside a row, the chain over the rows)."""
+    r, sub, test, args = _inputs(name)
+    res = ref_results[name]
+    r_u = sp.csr_matrix(sp.csr_matrix(r, dtype=np.float64).T)
+    r_u.sort_indices()
+    n = r_u.shape[0]
+    for a, b in ((0, n), (n // 3, n - 1), (2, 2)):
+        s64, c64 = ref.sse(r_u, res.users, res.items, a, b, a)
+        depth = 1 + int(np.diff(r_u.indptr).max()) + (b - a)
+        s, c, bound = ref.sse_ld(r_u, res.users, res.items, a, b, a,
+                                 depth=depth)
+        assert c == c64
+        assert abs(float(LD(s64) - s)) <= bound, (a, b)
+        assert bound <= 1e-12 * float(s) or s == 0
+
+
+def test_sse_ld_and_row_means_ld_rules():
+    users = np.array([[1.0, 2.0], [0.5, -1.0]], dtype=np.float32)
+    items = np.array([[1.0, 1.0], [2.0, 0.0], [np.nan, np.nan]],
+                     dtype=np.float32)
+    m = ref.Csr.from_rows([([0, 1, 2, -1], [5.0, 0.0, 1.0, 1.0]),
+                           ([1, 1], [2.0, -1.0]), ([], []), ([0], [0.0])], 3)
+    s, c, bound = ref.sse_ld(m, users, items, 0, 2, 0, n_items=2)
+    # (5 - 3)^2 + (2 - 1)^2 + (-1 - 1)^2: the NaN item and column -1 dropped
+    assert (float(s), c) == (9.0, 3) and 0 < bound < 1e-13
+    assert ref.sse_ld(m, users, items, 1, 2, 0, n_items=2)[:2] == (9.0, 2)
+    assert ref.sse_ld(m, users, items, 2, 2, 0)[:2] == (0.0, 0)
+    assert ref.sse_depth(129, 257) == 3 + 6 + 2 + 8
+    means = ref.row_means_ld(m)
+    assert means.dtype == LD
+    assert np.array_equal(means[[0, 1, 3]].astype(float), [1.75, 0.5, 0.0])
+    assert np.isnan(means[2])
+    assert np.array_equal(ref.row_means_bound(m),
+                          [(4 / 64 + 8) * U * 7 / 4, (2 / 64 + 8) * U * 3 / 2,
+                           0.0, 0.0])
