@@ -576,6 +576,25 @@ def merge_tree(osum, acc, f32):
 # ---------------------------------------------------------------------------
 # rows whose loads a dkm_col_chain_* chain issues together (CH_U)
 SCALE_CHAIN_TILE = 16
+# the grid of dkm_col_stats_* / dkm_scale_transform_*: a block per 16384
+# elements, 2048 blocks at the most (SC_GRID)
+SCALE_GRID_UNIT = 16384
+SCALE_GRID_CAP = 2048
+
+
+def scale_grid(n, d):
+    """Blocks of dkm_col_stats_* / dkm_scale_transform_* on (n, d): the
+    plan of dkm_scale.hip restated, for the tests to name the branch a
+    shape reaches."""
+    if n <= 0:
+        return 0
+    work = (n * d + SCALE_GRID_UNIT - 1) // SCALE_GRID_UNIT
+    return max(1, min(work, SCALE_GRID_CAP))
+
+
+def scale_workspace_bytes(n, d):
+    """dkm_scale_workspace_bytes restated: a partial per block and column."""
+    return (max(1, scale_grid(n, d)) * d * 8 + 255) // 256 * 256
 
 
 def scale_row_tile(d, dtype, vector=True):
@@ -689,6 +708,56 @@ GM_MSTEP_ROWS = 4
 def gm_estep_block(d):
     """Rows one block of dkm_gm_estep_* takes on d columns."""
     return 64 if 64 < d <= 128 else 128
+
+
+# the plan of dkm_gm.hip restated, for the tests to name the branch a shape
+# reaches: rows of an M-step chunk (at least), most chunks, the size the
+# covariance partials are capped at (about), threads of a block (the E-step's
+# final sum and the folds of the M-step take that many partials per trip)
+GM_CHUNK_ROWS = 512
+GM_MAX_CHUNKS = 2048
+GM_COV_WORKSPACE = 64 << 20
+GM_BLOCK = 256
+
+
+def gm_estep_blocks(n, d):
+    """Blocks of dkm_gm_estep_* on n rows of d columns."""
+    b = gm_estep_block(d)
+    return (n + b - 1) // b
+
+
+def gm_sums_chunks(n):
+    """Row chunks of dkm_gm_mstep_sums_*."""
+    return max(1, min((n + GM_CHUNK_ROWS - 1) // GM_CHUNK_ROWS,
+                      GM_MAX_CHUNKS))
+
+
+def gm_cov_tiles(d):
+    """16 x 16 tiles of a covariance on or above the diagonal."""
+    p = (d + 15) // 16
+    return p * (p + 1) // 2
+
+
+def gm_cov_chunks(n, d, k):
+    """Row chunks of dkm_gm_mstep_cov_*: the sums' chunks, capped so that
+    the partials (2048 B per chunk, component and tile) stay within about
+    GM_COV_WORKSPACE -- but never below 8."""
+    cap = max(8, GM_COV_WORKSPACE // (k * gm_cov_tiles(d) * 2048))
+    return max(1, min(gm_sums_chunks(n), cap))
+
+
+def gm_chunk_rows(n, chunks):
+    """Rows of an M-step chunk: a multiple of 4."""
+    return ((n + chunks - 1) // chunks + 3) // 4 * 4
+
+
+def gm_workspace_bytes(n, d, k):
+    """dkm_gm_workspace_bytes restated: the largest of the E-step's block
+    partials, the sums' partials and the covariances' partials."""
+    b = max(1, gm_estep_blocks(n, d)) * 8
+    b = max(b, gm_sums_chunks(n) * k * (d + 1) * 8)
+    b = max(b, gm_cov_chunks(n, d, k) * k * gm_cov_tiles(d) * 2048)
+    return (b + 255) // 256 * 256
 
 
 def gm_workspace(dd, k):

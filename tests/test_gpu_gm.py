@@ -40,11 +40,14 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _padded(x, ld):
+def _padded(x, ld, offset=0):
     """x in a device buffer with leading dimension ld (NaN in the padding:
-    a kernel that reads it shows)."""
-    buf = torch.full((max(1, x.shape[0]), ld), float("nan"),
-                     dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
+    a kernel that reads it shows), starting ``offset`` elements into its
+    allocation."""
+    rows = max(1, x.shape[0])
+    flat = torch.full((offset + rows * ld,), float("nan"),
+                      dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
+    buf = flat[offset:].view(rows, ld)
     buf[:x.shape[0], :x.shape[1]] = torch.from_numpy(x).cuda()
     return buf
 
@@ -68,21 +71,33 @@ def _model(rs, d, K, lower=False):
     return mu, pc, w, ldw
 
 
-class Kernels:
-    """The C ABI on one padded device matrix."""
+GUARD_BYTE = 0xA5
 
-    def __init__(self, x, pad, K):
+
+class Kernels:
+    """The C ABI on one padded device matrix, which starts ``offset``
+    elements into its allocation.  ``guard``: bytes behind a workspace of
+    exactly dkm_gm_workspace_bytes that every call must leave as they are."""
+
+    def __init__(self, x, pad, K, offset=0, guard=0):
         self.so = _lib.lib()
         self.f32 = x.dtype == np.float32
         self.d, self.ld, self.K = x.shape[1], x.shape[1] + pad, K
-        self.X = _padded(x, self.ld)
+        self.X = _padded(x, self.ld, offset)
+        self.guard = guard
 
     def _ws(self, n):
         nb = self.so.dkm_gm_workspace_bytes(n, self.d, self.K)
         assert nb > 0
-        return torch.empty(nb, dtype=torch.uint8, device="cuda"), nb
+        ws = torch.empty(nb + self.guard, dtype=torch.uint8, device="cuda")
+        ws[nb:] = GUARD_BYTE
+        return ws, nb
 
-    def estep(self, n, mu, pc, ldw, flags):
+    def _guard_kept(self, ws, nb):
+        assert bool((ws[nb:] == GUARD_BYTE).all())
+
+    def estep(self, n, mu, pc, ldw, flags, labels=True):
+        """(resp, labels, total); ``labels`` False passes labels = NULL."""
         fn = self.so.dkm_gm_estep_f32 if self.f32 else self.so.dkm_gm_estep_f64
         ws, nb = self._ws(n)
         resp = torch.full((max(n, 1), self.K), -7.0, dtype=torch.float64,
@@ -92,8 +107,12 @@ class Kernels:
         par = [_dev(a) for a in (mu, pc, ldw)]     # alive through the call
         _lib.check(fn(_p(self.X) if n else None, n, self.d, self.ld,
                       _p(par[0]), _p(par[1]), _p(par[2]), self.K,
-                      flags, _p(ws), nb, _p(resp), _p(lab), _p(tot), _st()),
+                      flags, _p(ws), nb, _p(resp),
+                      _p(lab) if labels else None, _p(tot), _st()),
                    "estep")
+        self._guard_kept(ws, nb)
+        if not labels:
+            assert bool((lab == -7).all())
         return (resp[:n].cpu().numpy(), lab[:n].cpu().numpy(),
                 float(tot.item()))
 
@@ -107,6 +126,7 @@ class Kernels:
         _lib.check(fn(_p(self.X) if n else None, n, self.d, self.ld, _p(r),
                       self.K, _p(ws), nb, _p(out), _st()), "sums")
         got = out.cpu().numpy()
+        self._guard_kept(ws, nb)
         assert got[-1] == -7.0
         return got[:self.K], got[self.K:-1].reshape(self.K, self.d)
 
@@ -120,7 +140,9 @@ class Kernels:
         mu = _dev(means)
         _lib.check(fn(_p(self.X) if n else None, n, self.d, self.ld, _p(r),
                       _p(mu), self.K, _p(ws), nb, _p(out), _st()), "cov")
-        return out.cpu().numpy()
+        got = out.cpu().numpy()
+        self._guard_kept(ws, nb)
+        return got
 
 
 def check_estep(x, n, mu, pc, ldw, got, truth):
@@ -154,17 +176,19 @@ def check_estep(x, n, mu, pc, ldw, got, truth):
     assert np.array_equal(lab, resp.argmax(axis=1) if n else lab)
 
 
-def check_mstep(kern, x, n, resp, means):
+def check_mstep(kern, x, n, resp, means, truth=None):
+    """``truth``: (nk, sums, cov) of the longdouble restatement on these
+    inputs, where the caller has them already."""
     x64 = x[:n].astype(np.float64)
     r = resp[:n]
     nk, s = kern.sums(n, resp)
-    tnk, ts = gr.mstep_sums(x[:n], r, LD)
+    tnk, ts = truth[:2] if truth else gr.mstep_sums(x[:n], r, LD)
     assert (np.abs((nk.astype(LD) - tnk).astype(np.float64)) <=
             (n + 8) * U * np.abs(r).sum(axis=0)).all()
     assert (np.abs((s.astype(LD) - ts).astype(np.float64)) <=
             (n + 8) * U * (np.abs(r).T @ np.abs(x64))).all()
     cov = kern.cov(n, resp, means)
-    tcov = gr.mstep_cov(x[:n], r, means, LD)
+    tcov = truth[2] if truth else gr.mstep_cov(x[:n], r, means, LD)
     for k in range(means.shape[0]):
         ad = np.abs(x64 - means[k])
         bound = (n + 8) * U * ((np.abs(r[:, k]) * ad.T) @ ad)

@@ -94,13 +94,20 @@ def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _padded(x, ld):
+def _padded(x, ld, offset=0):
     """x in a device buffer with leading dimension ld (NaN in the padding:
-    a kernel that reads it shows)."""
-    buf = torch.full((max(1, x.shape[0]), ld), float("nan"),
-                     dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
+    a kernel that reads it shows), starting ``offset`` elements into its
+    allocation."""
+    rows = max(1, x.shape[0])
+    flat = torch.full((offset + rows * ld,), float("nan"),
+                      dtype=torch.from_numpy(x[:0]).dtype, device="cuda")
+    buf = flat[offset:].view(rows, ld)
     buf[:x.shape[0], :x.shape[1]] = torch.from_numpy(x).cuda()
     return buf
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _edge_sizes(d, dtype, vector):
@@ -112,33 +119,23 @@ def _edge_sizes(d, dtype, vector):
     return sizes + [0, 3 * 16384 // d + 5]
 
 
-@pytest.mark.parametrize("pad", [0, 3, 4])
-@pytest.mark.parametrize("d", [2, 3, 32, 33, 64, 130])
-@pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_kernel_edges_against_the_restatement(dtype, d, pad):
+def check_chains(x, X, sizes):
+    """dkm_col_chain_*: x and (x - mean)^2 in the samples' dtype, exact, a
+    chain per (Subset of ``sizes``, column)."""
     so = _lib.lib()
-    f32 = dtype == np.float32
-    v = 16 // np.dtype(dtype).itemsize
-    vector = d % v == 0 and (d + pad) % v == 0
-    sizes = _edge_sizes(d, dtype, vector)
-    n, S = sum(sizes), len(sizes)
-    rs = np.random.RandomState(1000 * d + pad)
-    x = (rs.standard_normal((n, d)) * 3.0 + rs.uniform(-4, 4, d)).astype(dtype)
+    (n, d), ldx, S, dtype = x.shape, X.stride(0), len(sizes), x.dtype.type
     blocks = sr.split(x, sizes)
-    X = _padded(x, d + pad)
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(
         np.int64)).cuda()
     mean = x.mean(axis=0, dtype=np.float64)
-
-    # chains: x and (x - mean)^2 in the samples' dtype, exact
-    chain = so.dkm_col_chain_f32 if f32 else so.dkm_col_chain_f64
+    chain = so.dkm_col_chain_f32 if dtype == np.float32 else \
+        so.dkm_col_chain_f64
     ldp = d + 1
     for m in (None, mean.astype(dtype)):
         part = torch.full((S, ldp), -7.0, dtype=torch.float64, device="cuda")
         md = torch.from_numpy(m).cuda() if m is not None else None
-        _lib.check(chain(_p(X), n, d, d + pad, _p(md), _p(off), S, _p(part),
-                         ldp, st), "chain")
+        _lib.check(chain(_p(X), n, d, ldx, _p(md), _p(off), S, _p(part),
+                         ldp, _stream()), "chain")
         got = part.cpu().numpy()
         assert (got[:, d] == -7.0).all()          # beyond d: untouched
         for s, b in enumerate(blocks):
@@ -146,44 +143,96 @@ def test_kernel_edges_against_the_restatement(dtype, d, pad):
             assert want.dtype == dtype
             assert np.array_equal(got[s, :d], want.astype(np.float64)), s
 
-    # fast statistics: fp64 sums in another order.  Any order of n fp64 adds
-    # is within (n - 1) 2^-53 sum|t| of the exact sum; a term (x - m)^2 adds
-    # 3 roundings of its own: (n + 3) 2^-53 sum|t|, doubled for the
-    # yardstick's own (pairwise) error
-    stats = so.dkm_col_stats_f32 if f32 else so.dkm_col_stats_f64
+
+def check_stats(x, X):
+    """dkm_col_stats_*: fp64 sums in another order.  Any order of n fp64
+    adds is within (n - 1) 2^-53 sum|t| of the exact sum; a term (x - m)^2
+    adds 3 roundings of its own: (n + 3) 2^-53 sum|t|, doubled for the
+    yardstick's own (pairwise) error.  A rerun gives the same bytes."""
+    so = _lib.lib()
+    (n, d), ldx = x.shape, X.stride(0)
+    stats = so.dkm_col_stats_f32 if x.dtype == np.float32 else \
+        so.dkm_col_stats_f64
     nws = so.dkm_scale_workspace_bytes(n, d)
     ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
     x64 = x.astype(np.float64)
+    mean = x.mean(axis=0, dtype=np.float64)
     for m in (None, mean):
         out = torch.full((d,), -7.0, dtype=torch.float64, device="cuda")
         md = torch.from_numpy(m).cuda() if m is not None else None
         res = []
         for _ in range(2):
-            _lib.check(stats(_p(X), n, d, d + pad, _p(md), _p(ws), nws,
-                             _p(out), st), "stats")
+            _lib.check(stats(_p(X), n, d, ldx, _p(md), _p(ws), nws,
+                             _p(out), _stream()), "stats")
             res.append(out.cpu().numpy())
         assert res[0].tobytes() == res[1].tobytes()
         terms = x64 if m is None else (x64 - m) ** 2
         bound = 2 * (n + 3) * 2.0 ** -53 * np.abs(terms).sum(axis=0)
         assert (np.abs(res[0] - terms.sum(axis=0)) <= bound).all()
 
-    # the scaling: numpy's own correctly rounded arithmetic, exact
+
+def scale_pairings(dtype):
+    """(statistics' dtype, entry's suffix): the samples' own dtype and the
+    other one."""
+    f32 = dtype == np.float32
+    return ((dtype, "f32" if f32 else "f64"),
+            (np.float64 if f32 else np.float32,
+             "f32_f64" if f32 else "f64_f32"))
+
+
+def check_scaling(x, X, pairings=None, ypad=None, yoff=0, in_place=False):
+    """dkm_scale_transform_*: numpy's own correctly rounded arithmetic,
+    exact, and Y's padding untouched.  Y has ``ypad`` padding columns (X's
+    by default) and starts ``yoff`` elements into its allocation;
+    ``in_place`` also runs the call on a copy of X's buffer with Y = X and
+    requires the same bytes."""
+    so = _lib.lib()
+    (n, d), ldx, dtype = x.shape, X.stride(0), x.dtype.type
+    ldy = ldx if ypad is None else d + ypad
+    x64 = x.astype(np.float64)
+    mean = x.mean(axis=0, dtype=np.float64)
     var = ((x64 - mean) ** 2).mean(axis=0)
-    for sdt, name in ((dtype, "f32" if f32 else "f64"),
-                      (np.float64 if f32 else np.float32,
-                       "f32_f64" if f32 else "f64_f32")):
+    for sdt, name in pairings or scale_pairings(dtype):
         m, w = mean.astype(sdt), var.astype(sdt)
         want = (x - m) / np.sqrt(w)
-        Y = torch.full((n, d + pad), -7.0, device="cuda",
-                       dtype=torch.from_numpy(want[:0]).dtype)
+        flat = torch.full((yoff + n * ldy,), -7.0, device="cuda",
+                          dtype=torch.from_numpy(want[:0]).dtype)
+        Y = flat[yoff:].view(n, ldy)
         fn = getattr(so, "dkm_scale_transform_" + name)
         md, wd = torch.from_numpy(m).cuda(), torch.from_numpy(w).cuda()
-        _lib.check(fn(_p(X), n, d, d + pad, _p(md), _p(wd), _p(Y), d + pad,
-                      st), name)
+        _lib.check(fn(_p(X), n, d, ldx, _p(md), _p(wd), _p(Y), ldy,
+                      _stream()), name)
         got = Y.cpu().numpy()
         assert got.dtype == want.dtype
         assert np.array_equal(got[:, :d], want), name
         assert (got[:, d:] == -7.0).all()
+        assert (flat[:yoff] == -7.0).all()
+        if in_place:
+            assert want.dtype == dtype and ldy == ldx
+            Z = X.clone()
+            assert Z.stride(0) == ldx and Z.data_ptr() % 16 == \
+                X.data_ptr() % 16
+            _lib.check(fn(_p(Z), n, d, ldx, _p(md), _p(wd), _p(Z), ldx,
+                          _stream()), name)
+            z = Z.cpu().numpy()
+            assert z[:n, :d].tobytes() == got[:, :d].tobytes()
+            assert np.isnan(z[:n, d:]).all()      # X's padding: NaN as before
+
+
+@pytest.mark.parametrize("pad", [0, 3, 4])
+@pytest.mark.parametrize("d", [2, 3, 32, 33, 64, 130])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_kernel_edges_against_the_restatement(dtype, d, pad):
+    v = 16 // np.dtype(dtype).itemsize
+    vector = d % v == 0 and (d + pad) % v == 0
+    sizes = _edge_sizes(d, dtype, vector)
+    n = sum(sizes)
+    rs = np.random.RandomState(1000 * d + pad)
+    x = (rs.standard_normal((n, d)) * 3.0 + rs.uniform(-4, 4, d)).astype(dtype)
+    X = _padded(x, d + pad)
+    check_chains(x, X, sizes)
+    check_stats(x, X)
+    check_scaling(x, X)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
