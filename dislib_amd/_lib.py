@@ -22,6 +22,7 @@ BOUNDS_INIT = 1
 GM_UPPER = 1
 DBSCAN_NOPRUNE = 1
 ALS_MAX_NF, ALS_CHUNK = 128, 16
+SVM_LINEAR, SVM_RBF, SVM_QMAX = 0, 1, 128
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -174,6 +175,25 @@ SIGNATURES = {
     "dkm_als_sse": (_i32, [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _i64,
                            _i64, _p, _sz, _p, _p]),
     "dkm_als_row_means": (_i32, [_p, _p, _i64, _p, _p]),
+    # CascadeSVM: kernel rows, working set, local SMO, decision values, W
+    "dkm_svm_norms_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p]),
+    "dkm_svm_norms_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p]),
+    "dkm_svm_rows_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p,
+                                _i32, _f64, _p, _i64, _p]),
+    "dkm_svm_rows_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p,
+                                _i32, _f64, _p, _i64, _p]),
+    "dkm_svm_select": (_i32, [_p, _p, _p, _i64, _f64, _i64, _p, _p, _p, _p]),
+    "dkm_svm_local": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _f64, _f64,
+                             _i64, _p, _p, _p]),
+    "dkm_svm_update": (_i32, [_p, _i64, _i64, _p, _p, _i64, _p]),
+    "dkm_svm_decision_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64,
+                                    _i64, _p, _i64, _p, _f64, _p, _p, _i32,
+                                    _f64, _p, _p]),
+    "dkm_svm_decision_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _i64,
+                                    _i64, _p, _i64, _p, _f64, _p, _p, _i32,
+                                    _f64, _p, _p]),
+    "dkm_svm_w": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
+                         _i32, _f64, _p, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

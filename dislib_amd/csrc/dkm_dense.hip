@@ -3788,7 +3788,7 @@ int dkm_build_flags(void) {
          tu_flags_sorted() | tu_flags_cand() | tu_flags_sparse() |
          tu_flags_gemm() | tu_flags_sums() | tu_flags_neighbors() |
          tu_flags_ordered() | tu_flags_scale() | tu_flags_gm() |
-         tu_flags_dbscan() | tu_flags_als();
+         tu_flags_dbscan() | tu_flags_als() | tu_flags_svm();
 }
 
 }  // extern "C"

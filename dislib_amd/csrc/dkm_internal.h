@@ -35,6 +35,7 @@ int preload_scale();
 int preload_gm();
 int preload_dbscan();
 int preload_als();
+int preload_svm();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -64,6 +65,7 @@ int tu_flags_scale();
 int tu_flags_gm();
 int tu_flags_dbscan();
 int tu_flags_als();
+int tu_flags_svm();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

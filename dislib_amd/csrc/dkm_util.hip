@@ -640,7 +640,7 @@ int dkm_preload(void) {
          preload_sorted() + preload_cand() + preload_sparse() +
          preload_gemm() + preload_sums() + preload_neighbors() +
          preload_ordered() + preload_scale() + preload_gm() +
-         preload_dbscan() + preload_als();
+         preload_dbscan() + preload_als() + preload_svm();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

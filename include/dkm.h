@@ -798,6 +798,92 @@ int dkm_als_row_means(const int64_t *indptr, const double *data,
                       int64_t n_rows, double *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * CascadeSVM: what a node of the cascade needs in place of
+ * sklearn.svm.SVC (dislib/classification/csvm/base.py:331-346), the decision
+ * values of :350-366 and the convergence quantity of :259-274.  Binary
+ * C-SVC.  X is the resident n x d sample matrix (row stride ldx >= d); a
+ * node is rows[m], int32 indices into X in any order; node vectors (y, alpha,
+ * f) are indexed by the position inside the node.  y is +1 / -1 as fp64,
+ * f_i = sum_j alpha_j y_j K_ij - y_i (y times the dual gradient; -y with
+ * alpha = 0), so libsvm's -y_i G_i is -f_i.  An index outside its range
+ * names a row of zeros and is never dereferenced.  Every sum has a fixed
+ * order: results are identical from run to run.
+ * --------------------------------------------------------------------- */
+
+#define DKM_SVM_LINEAR 0  /* x_i . x_j                                        */
+#define DKM_SVM_RBF 1     /* exp(-gamma (|x_i|^2 + |x_j|^2 - 2 x_i . x_j))     */
+/* Largest working set: its q x q block of K (128 KiB) and the staging of the
+ * other kernels fit the 160 KiB of LDS. */
+#define DKM_SVM_QMAX 128
+/* out[i] (fp64) <- |x_i|^2 of every row (an fma chain over the row). */
+int dkm_svm_norms_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                      double *out, void *stream);
+int dkm_svm_norms_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                      double *out, void *stream);
+/* K[a * ldk + j] (fp64, q x m, ldk >= m) <- K(x_rows[ws[a]], x_rows[j]) for
+ * the working set ws[q] (positions inside the node; a negative entry is an
+ * empty slot whose row of K is not meaningful), 1 <= q <= DKM_SVM_QMAX.
+ * norms: dkm_svm_norms_* of X (rbf only).  The dot products run on the fp64
+ * MFMA. */
+int dkm_svm_rows_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                     const int32_t *rows, int64_t m, const int32_t *ws,
+                     int64_t q, const double *norms, int kernel, double gamma,
+                     double *K, int64_t ldk, void *stream);
+int dkm_svm_rows_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                     const int32_t *rows, int64_t m, const int32_t *ws,
+                     int64_t q, const double *norms, int kernel, double gamma,
+                     double *K, int64_t ldk, void *stream);
+/* Working-set selection.  I_up = {y = +1, alpha < C} u {y = -1, alpha > 0},
+ * I_low = {y = +1, alpha > 0} u {y = -1, alpha < C}.  gap[0] <- m(alpha) -
+ * M(alpha) = max_{I_up} -f - min_{I_low} -f (-inf when either set is empty),
+ * gap[1] <- m(alpha), gap[2] <- M(alpha).  ws[0 .. q/2) <- the positions of
+ * I_up with the largest -f, ws[q/2 .. 2 (q/2)) <- those of I_low with the
+ * smallest -f, taken in turns (up, low, up, ...) so that no position is taken
+ * twice; ties go to the lower position; -1 where a set ran out and in the
+ * last slot of an odd q.  q >= m: ws = 0 .. m-1, then -1.  mark: m int32 of
+ * scratch.  2 <= q <= DKM_SVM_QMAX. */
+int dkm_svm_select(const double *f, const double *alpha, const double *y,
+                   int64_t m, double C, int64_t q, int32_t *ws, double *gap,
+                   int32_t *mark, void *stream);
+/* SMO on the working set, one workgroup: libsvm's second-order pair choice
+ * (WSS2, TAU = 1e-12 where the curvature is not positive) and two-variable
+ * update with clipping to [0, C], on the q x q block K[a * ldk + ws[b]] of
+ * dkm_svm_rows_*, until the working set's m - M < eps or max_inner steps.
+ * alpha[ws[.]] is updated in place, dy[q] <- y o (alpha_new - alpha_old) (0
+ * in empty slots), info[0] <- steps taken, info[1] <- 1 if max_inner ended
+ * the loop.  f is read, not written: dkm_svm_update applies dy. */
+int dkm_svm_local(const double *K, int64_t ldk, const int32_t *ws, int64_t q,
+                  const double *y, double *alpha, const double *f, int64_t m,
+                  double C, double eps, int64_t max_inner, double *dy,
+                  int32_t *info, void *stream);
+/* f[j] += sum_t K[t * ldk + j] dy[t] for j < m, t ascending (fma). */
+int dkm_svm_update(const double *K, int64_t ldk, int64_t q, const double *dy,
+                   double *f, int64_t m, void *stream);
+/* out[i] (fp64) <- sum_s coef[s] K(q_i, x_sv[s]) + b for the nq rows of Q
+ * (row stride ldq) against the ns support rows sv[] of X (fp32 when x_f32,
+ * else fp64).  qnorm / xnorm: dkm_svm_norms_* of Q and X (rbf only).  The
+ * products run on the fp64 MFMA; the sum over s has a fixed order. */
+int dkm_svm_decision_f64(const double *Q, int64_t nq, int64_t d, int64_t ldq,
+                         const void *X, int x_f32, int64_t n, int64_t ldx,
+                         const int32_t *sv, int64_t ns, const double *coef,
+                         double b, const double *qnorm, const double *xnorm,
+                         int kernel, double gamma, double *out, void *stream);
+int dkm_svm_decision_f32(const float *Q, int64_t nq, int64_t d, int64_t ldq,
+                         const void *X, int x_f32, int64_t n, int64_t ldx,
+                         const int32_t *sv, int64_t ns, const double *coef,
+                         double b, const double *qnorm, const double *xnorm,
+                         int kernel, double gamma, double *out, void *stream);
+/* W[0] <- -0.5 sum_ij c_i c_j l_i l_j K'(x_sv[i], x_sv[j]) + sum_i c_i, the
+ * reference's _lagrangian_fast: c = coef (the signed dual coefficients), l =
+ * lab (its labels), K' the reference's own kernels -- linear, or its
+ * _rbf_kernel, which evaluates to exp(+gamma |x_i - x_j|^2).  tmp: ns fp64
+ * of scratch. */
+int dkm_svm_w(const void *X, int x_f32, int64_t n, int64_t d, int64_t ldx,
+              const int32_t *sv, int64_t ns, const double *coef,
+              const double *lab, const double *xnorm, int kernel, double gamma,
+              double *tmp, double *W, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
