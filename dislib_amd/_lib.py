@@ -23,6 +23,8 @@ GM_UPPER = 1
 DBSCAN_NOPRUNE = 1
 ALS_MAX_NF, ALS_CHUNK = 128, 16
 SVM_LINEAR, SVM_RBF, SVM_QMAX = 0, 1, 128
+RF_MAX_CLASSES, RF_MAX_SAMPLES, RF_LDS_MAX = 32, 1 << 24, 32768
+RF_AUTO, RF_LDS, RF_STREAM = 0, 1, 2
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -194,6 +196,16 @@ SIGNATURES = {
                                     _f64, _p, _p]),
     "dkm_svm_w": (_i32, [_p, _i32, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
                          _i32, _f64, _p, _p, _p]),
+    # RandomForestClassifier: split search, best of a node, partition, predict
+    "dkm_rf_split": (_i32, [_p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p,
+                            _i64, _i64, _i32, _p, _p, _p]),
+    "dkm_rf_best": (_i32, [_p, _p, _p, _p, _p, _i64, _p, _p]),
+    "dkm_rf_partition": (_i32, [_p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p,
+                                _p, _p]),
+    "dkm_rf_predict_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
+                                  _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    "dkm_rf_predict_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
+                                  _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

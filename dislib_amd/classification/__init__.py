@@ -1,3 +1,4 @@
 from .csvm import CascadeSVM
+from .rf import RandomForestClassifier
 
-__all__ = ["CascadeSVM"]
+__all__ = ["CascadeSVM", "RandomForestClassifier"]

@@ -884,6 +884,76 @@ int dkm_svm_w(const void *X, int x_f32, int64_t n, int64_t d, int64_t ldx,
               double *tmp, double *W, void *stream);
 
 /* ------------------------------------------------------------------------
+ * RandomForestClassifier: exact CART growth on per-feature
+ * dense ranks, level by level over the trees of a batch, and the forest's
+ * prediction.  rank / order: d x n int32, feature-major; rank[f][s] is the
+ * dense rank of sample s in feature f, order[f][.] the samples by ascending
+ * value.  y[n]: class codes < C.  Per tree of the batch (row stride n):
+ * members, the tree's samples listed once per bootstrap draw and segmented by
+ * node; node_of[s], the number of the node that holds sample s (-1: none);
+ * weight[s], the draws of sample s.  nodes[i] = {tree, start, size, id}: node
+ * i of the level is members[tree][start .. start + size) and node_of == id.
+ * ncounts[i][C]: its class counts.  Integer sums only: results are identical
+ * from run to run and between the two regimes.
+ * --------------------------------------------------------------------- */
+
+#define DKM_RF_MAX_CLASSES 32        /* a key is rank * 32 + class ...       */
+#define DKM_RF_MAX_SAMPLES (1 << 24) /* ... in 32 bits: n < 2^24             */
+/* Largest node of the LDS regime: a 32-bit key per member (128 KiB) next to
+ * the counters of the scan in the 160 KiB of LDS. */
+#define DKM_RF_LDS_MAX 32768
+#define DKM_RF_AUTO 0   /* LDS regime up to DKM_RF_LDS_MAX members, else stream */
+#define DKM_RF_LDS 1    /* every pair in LDS (max_size <= DKM_RF_LDS_MAX)     */
+#define DKM_RF_STREAM 2 /* every pair walks the feature's sorted order        */
+/* For every pair p = {node, feature} of pairs[n_pairs][2]: score[p] <- the
+ * smallest Gini proxy -(sum_c L_c^2 / |L| + sum_c R_c^2 / |R|) over the cuts
+ * between distinct ranks and the position size - 1 (|R| read as 1 there),
+ * the last position among equals; cut[p] = {position, the rank left of the
+ * cut, the rank right of it}.  Position size - 1: no valid cut.  max_size:
+ * the largest size among the nodes. */
+int dkm_rf_split(const int32_t *rank, const int32_t *order, int64_t n,
+                 const int32_t *y, int64_t C, const int32_t *members,
+                 const int32_t *node_of, const int32_t *weight,
+                 const int32_t *nodes, const int32_t *ncounts,
+                 const int32_t *pairs, int64_t n_pairs, int64_t max_size,
+                 int mode, double *score, int32_t *cut, void *stream);
+/* best[i] = {feature, rank left, rank right, left size} of the first strictly
+ * smallest score among node i's pairs pspan[i] = {first pair, pairs}, feature
+ * -1 when that pair has no valid cut. */
+int dkm_rf_best(const int32_t *nodes, const int32_t *pspan,
+                const int32_t *pairs, const double *score, const int32_t *cut,
+                int64_t n_nodes, int32_t *best, void *stream);
+/* Every node with a cut: members_out <- its segment with the members of rank
+ * <= best[i][1] first, in their order, node_of <- id (left) / id + 1 (right),
+ * lcounts[i][C] <- the left side's class counts.  Other nodes are copied. */
+int dkm_rf_partition(const int32_t *rank, int64_t n, const int32_t *y,
+                     int64_t C, const int32_t *nodes, const int32_t *best,
+                     int64_t n_nodes, const int32_t *members_in,
+                     int32_t *members_out, int32_t *node_of, int32_t *lcounts,
+                     void *stream);
+/* The forest on the rows of X.  Node v: feature[v] >= 0 sends a row with
+ * x[feature] <= value[v] to child[2 v], else to child[2 v + 1]; feature[v] <
+ * 0 is leaf number child[2 v] with freq[leaf][C], lsize[leaf], lmode[leaf].
+ * proba[r][C] <- the mean over the T trees (roots[T]) of freq / lsize, added
+ * in tree order; labels[r] <- the first argmax of those sums, or with hard
+ * the class most trees vote for (ties: the class voted first); votes[n][T]
+ * (hard only) <- every tree's mode. */
+int dkm_rf_predict_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                       const int32_t *roots, int64_t T, const int32_t *feature,
+                       const double *value, const int32_t *child,
+                       const int32_t *freq, const int32_t *lsize,
+                       const int32_t *lmode, int64_t C, int hard,
+                       double *proba, int32_t *votes, int32_t *labels,
+                       void *stream);
+int dkm_rf_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                       const int32_t *roots, int64_t T, const int32_t *feature,
+                       const double *value, const int32_t *child,
+                       const int32_t *freq, const int32_t *lsize,
+                       const int32_t *lmode, int64_t C, int hard,
+                       double *proba, int32_t *votes, int32_t *labels,
+                       void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
