@@ -17,22 +17,24 @@ from dislib_amd._shard import shard_dataset, shard_range  # noqa: E402,F401
 
 def install_as_dislib():
     """Alias ``dislib``, ``dislib.cluster``, ``dislib.data``,
-    ``dislib.neighbors``, ``dislib.preprocessing`` and
-    ``dislib.recommendation`` to this package (the k-means path, its data
-    containers, the kNN reuse of its distance primitive, the StandardScaler
-    and ALS)."""
+    ``dislib.neighbors``, ``dislib.preprocessing``,
+    ``dislib.recommendation`` and ``dislib.fft`` to this package (the
+    k-means path, its data containers, the kNN reuse of its distance
+    primitive, the StandardScaler, ALS and the FFT)."""
     import types
-    from dislib_amd import (cluster, data, neighbors, preprocessing,
+    from dislib_amd import (cluster, data, fft, neighbors, preprocessing,
                             recommendation)
     pkg = types.ModuleType("dislib")
     pkg.__path__ = []
     pkg.name = "dislib"
     pkg.cluster = cluster
     pkg.data = data
+    pkg.fft = fft
     pkg.neighbors = neighbors
     pkg.preprocessing = preprocessing
     pkg.recommendation = recommendation
     sys.modules["dislib"] = pkg
+    sys.modules["dislib.fft"] = fft
     sys.modules["dislib.preprocessing"] = preprocessing
     sys.modules["dislib.recommendation"] = recommendation
     sys.modules["dislib.neighbors"] = neighbors

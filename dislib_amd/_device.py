@@ -828,6 +828,75 @@ def gm_mstep_cov(dd, resp, means, ws, cov):
                   ptr(cov), stream_ptr()), "dkm_gm_mstep_cov")
 
 
+# fft: a block of dkm_fft.hip holds FFT_PTS points; longer transforms take
+# one or two outer passes of radix <= 256 before the LDS kernel
+FFT_PTS, FFT_MAX_N = 4096, 1 << 28
+_FFT_TWIDDLES = {}
+
+
+def fft_plan(n):
+    """The radices of dkm_fft_z's passes on a transform of length ``n`` (a
+    power of two, 1 .. 2**28), restated: the outer passes (k_fft_cols), then
+    the length the LDS kernel transforms.  A function of ``n`` only."""
+    e = int(n).bit_length() - 1
+    if n < 1 or n != 1 << e or n > FFT_MAX_N:
+        raise ValueError("fft_plan: n = %d is not a power of two in "
+                         "[1, 2**28]" % n)
+    if e <= 12:
+        return [n]
+    if e <= 20:
+        r = 1 << min(8, e - 8)
+        return [r, n // r]
+    m = 1 << max(8, e - 16)
+    return [256, n // m // 256, m]
+
+
+def fft_twiddles(n, device):
+    """The device table exp(-2 pi i k / n), k < n (dkm_fft_twiddles: long
+    double on the host, rounded once), cached per (n, device)."""
+    t = torch()
+    key = (int(n), t.device(device).index)
+    tw = _FFT_TWIDDLES.get(key)
+    if tw is None:
+        host = t.empty(int(n), dtype=t.complex128, pin_memory=True)
+        _lib.check(_lib.lib().dkm_fft_twiddles(int(n), ptr(host)),
+                   "dkm_fft_twiddles")
+        tw = _alloc("fft_twiddles", 16 * int(n),
+                    lambda: host.to(device, non_blocking=False))
+        _FFT_TWIDDLES[key] = tw
+    return tw
+
+
+def fft_z(x, n, batch):
+    """The transforms of the ``batch`` rows of length ``n`` of ``x`` (device
+    complex128, contiguous) as a new device tensor; ``x`` is not written.
+    ValueError when the buffers would leave less than 4 GiB of HBM free (the
+    rule of sums="reference")."""
+    t = torch()
+    so = _lib.lib()
+    n, batch = int(n), int(batch)
+    nws = int(so.dkm_fft_workspace_bytes(n, batch))
+    if nws == 0:
+        raise _lib.DkmError("dkm_fft_workspace_bytes: bad n/batch")
+    key = (n, x.device.index)
+    nb = 16 * n * batch + nws + (0 if key in _FFT_TWIDDLES else 16 * n)
+    free = t.cuda.mem_get_info(x.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        raise ValueError(
+            "fft of %d x %d complex128 needs %.2f GiB of HBM for its output, "
+            "workspace and twiddles, and %.2f GiB are free (4 GiB stay free)"
+            % (batch, n, nb / 2.0 ** 30, free / 2.0 ** 30))
+    with on(x.device):
+        preload(x.device)
+        tw = fft_twiddles(n, x.device)
+        out = t.empty(x.shape, dtype=t.complex128, device=x.device)
+        ws = _alloc("fft", nws, lambda: t.empty(nws, dtype=t.uint8,
+                                                device=x.device))
+        _lib.check(so.dkm_fft_z(ptr(x), ptr(out), n, batch, ptr(tw), ptr(ws),
+                                nws, stream_ptr()), "dkm_fft_z")
+    return out
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

@@ -206,6 +206,10 @@ SIGNATURES = {
                                   _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     "dkm_rf_predict_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
                                   _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    # fft: workspace size, the host twiddle table, the batched transform
+    "dkm_fft_workspace_bytes": (_sz, [_i64, _i64]),
+    "dkm_fft_twiddles": (_i32, [_i64, _p]),
+    "dkm_fft_z": (_i32, [_p, _p, _i64, _i64, _p, _p, _sz, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

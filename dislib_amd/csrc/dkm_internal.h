@@ -37,6 +37,7 @@ int preload_dbscan();
 int preload_als();
 int preload_svm();
 int preload_rf();
+int preload_fft();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -68,6 +69,7 @@ int tu_flags_dbscan();
 int tu_flags_als();
 int tu_flags_svm();
 int tu_flags_rf();
+int tu_flags_fft();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

@@ -954,6 +954,32 @@ int dkm_rf_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                        void *stream);
 
 /* ------------------------------------------------------------------------
+ * fft (dislib/fft/base.py): batched one-dimensional complex
+ * FFT in fp64, X[k] = sum_j x[j] exp(-2 pi i j k / n), for n a power of two
+ * up to 2^28, on interleaved complex128 (re, im pairs, 16-byte aligned).
+ * --------------------------------------------------------------------- */
+
+/* Bytes of workspace for `batch` transforms of length n: one buffer of
+ * n * batch complex values when n > 4096 (the passes alternate between it
+ * and the output), a nominal 256 otherwise.  0 if n is not a power of two
+ * in [1, 2^28] or batch < 1. */
+size_t dkm_fft_workspace_bytes(int64_t n, int64_t batch);
+
+/* HOST function: out[2 k], out[2 k + 1] <- re, im of exp(-2 pi i k / n),
+ * k < n, evaluated in long double and rounded once.  The one table serves
+ * every pass of dkm_fft_z (a pass of size m reads entry k n / m); upload it
+ * once per n. */
+int dkm_fft_twiddles(int64_t n, double *out);
+
+/* out[b n + k] <- the transform of in[b n .. b n + n), b < batch.  Out of
+ * place (`in` is not written; in != out), stream-ordered, asynchronous, no
+ * atomics (bit-identical from run to run).  `twiddles` is the device copy
+ * of dkm_fft_twiddles(n).  DKM_E_ARG for a bad shape or pointer,
+ * DKM_E_WORKSPACE if n > 4096 and ws_bytes < dkm_fft_workspace_bytes. */
+int dkm_fft_z(const void *in, void *out, int64_t n, int64_t batch,
+              const void *twiddles, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
