@@ -975,3 +975,17 @@ def screen_lists(ws):
     _lib.check(so.dkm_screen_lists(ws.p, ws.nbytes, out, stream_ptr()),
                "dkm_screen_lists")
     return tuple(int(x) for x in out)
+
+
+def list_stats(ws):
+    """(list re-check launches of this process in the tile form, in the lane
+    form, entries per list segment of the last one: a numpy int32 array)
+    (dkm_list_stats; diagnostics)."""
+    import numpy as np
+    so = _lib.lib()
+    out = (ctypes.c_int64 * 3)()
+    seg = np.zeros(8192, dtype=np.int32)
+    _lib.check(so.dkm_list_stats(ws.p, ws.nbytes, out,
+                                 seg.ctypes.data_as(ctypes.c_void_p),
+                                 seg.size, stream_ptr()), "dkm_list_stats")
+    return int(out[0]), int(out[1]), seg[:min(int(out[2]), seg.size)].copy()

@@ -402,6 +402,11 @@ __host__ __device__ inline int64_t dpad16(int64_t d) { return (d + 15) / 16 * 16
 __host__ __device__ inline int64_t dpad32(int64_t d) { return (d + 31) / 32 * 32; }
 __host__ __device__ inline int64_t dpad64(int64_t d) { return (d + 63) / 64 * 64; }
 
+// dkm_recheck.hip: list re-check launches of this process so far, out[0] in
+// the tile form (k_recheck_tile), out[1] in the lane form (k_recheck_list),
+// and out[2] the list segments of the last one (dkm_list_stats)
+void list_launch_stats(int64_t *out);
+
 size_t ws_bytes(int64_t k, int64_t d, int64_t n_queue);
 int64_t default_queue(int64_t k, int64_t d);
 int ws_view(const void *ws, size_t bytes, int64_t k, int64_t d, WsView *v);

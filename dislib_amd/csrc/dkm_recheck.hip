@@ -1,10 +1,13 @@
 // dkm_recheck.hip -- the samples a screen leaves undecided: k_recheck_list
-// (the screens' per-wave lists), k_recheck_wave, k_recheck_lane and
-// k_recheck_exact (the label scan).
+// and, at d <= 32, its tile form k_recheck_tile (the screens' per-wave
+// lists), k_recheck_wave, k_recheck_lane and k_recheck_exact (the label
+// scan).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
+#include <cstdlib>
 
 #include "dkm_dense.h"
 #include "dkm_screen.h"
@@ -320,8 +323,9 @@ static size_t recheck_lane_lds(int64_t, int64_t) {
   return (size_t)(BLOCK / 64) * RL_CAP * 8;
 }
 
-// k_recheck_lane and k_recheck_list, and their forms for a bounds call
-// (k_recheck_lane_bnd, k_recheck_list_bnd; d <= 32 only)
+// k_recheck_lane, k_recheck_list and k_recheck_tile, and their forms for a
+// bounds call (k_recheck_lane_bnd, k_recheck_list_bnd, k_recheck_tile_bnd;
+// d <= 32 only)
 #define RC_BND 0
 #include "dkm_recheck_kernels.inc"
 #undef RC_BND
@@ -521,6 +525,46 @@ static int launch_list_bnd_t(const TX *X, int d, int64_t ldx, int k,
   return check_launch("list re-check (bounds)");
 }
 
+// k_recheck_tile / k_recheck_tile_bnd (rb set): the tile form of the list
+// re-check at d <= 32.  No counter reset: it feeds no k_recheck_wave.
+template <bool VEC, class TX>
+static int launch_tile_t(const TX *X, int d, int64_t ldx, int k,
+                         const WsView &v, int32_t *lab_out, double *acc,
+                         int amode, int64_t base, int nseg, size_t lds,
+                         hipStream_t s, const RcBnd *rb) {
+  const void *kf = rb ? (const void *)k_recheck_tile_bnd<VEC, TX>
+                      : (const void *)k_recheck_tile<VEC, TX>;
+  if (hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)lds) != hipSuccess)
+    return fail(DKM_E_LAUNCH, "list re-check (tiles): LDS size");
+  const int per_cu = resident_blocks(kf, BLOCK, lds);
+  const int64_t units = (int64_t)nseg * (TL_CAP / 64);
+  const int64_t g = std::max<int64_t>(
+      1, std::min<int64_t>((int64_t)dev_info().cus * per_cu,
+                           (units + BLOCK / 64 - 1) / (BLOCK / 64)));
+  if (rb)
+    k_recheck_tile_bnd<VEC, TX><<<(unsigned)g, BLOCK, lds, s>>>(
+        X, d, ldx, k, v, lab_out, acc, amode, base, nseg, *rb);
+  else
+    k_recheck_tile<VEC, TX><<<(unsigned)g, BLOCK, lds, s>>>(
+        X, d, ldx, k, v, lab_out, acc, amode, base, nseg);
+  return check_launch("list re-check (tiles)");
+}
+
+// what dkm_list_stats reports (tests tell the two forms apart by it)
+static std::atomic<int64_t> g_list_stats[3];
+void list_launch_stats(int64_t *out) {
+  for (int i = 0; i < 3; ++i) out[i] = g_list_stats[i].load();
+}
+
+// DKM_RECHECK_TILE=0 in the environment (read at every call, for A/B runs):
+// the list re-check at d <= 32 runs its lane-per-row stage 1 (k_recheck_list)
+// instead of the tile form
+static bool recheck_tile() {
+  const char *e = getenv("DKM_RECHECK_TILE");
+  return !(e && e[0] == '0' && !e[1]);
+}
+
 // Can the listed samples be resolved lane-per-sample (k_recheck_list)?
 bool list_ok(int64_t k, int64_t d) {
   return d <= 128 && recheck_lane_lds(k, d) <= LDS_BUDGET;
@@ -540,9 +584,28 @@ int launch_list(const TX *X, int d, int64_t ldx, int k, const WsView &v,
   const int amode = acc_mode(acc_kind, fb + a_bytes <= LDS_BUDGET);
   const size_t lds = fb + ((amode & AM_INLDS) ? a_bytes : 0);
   const int maxd = d <= 32 ? 32 : d <= 64 ? 64 : 128;
+  if (bnd && (maxd != 32 || wave_all))
+    return fail(DKM_E_ARG, "list re-check: bounds need d <= 32");
+  // the tile form: d <= 32, a long list, its fragments and transposes fit
+  // (k <= 480), and the sums keep the LDS place the lane form gives them
+  // (at d = 32: k <= 159; beyond, fp64 global atomics on k rows would
+  // serialise what the lane form adds in LDS)
+  const size_t tb = recheck_tile_lds(k);
+  const bool sums_stay = acc_kind == 0 || tb + a_bytes <= LDS_BUDGET ||
+                         a_bytes > LDS_BUDGET;
+  g_list_stats[2] = nseg;
+  if (maxd == 32 && !wave_all && tb <= LDS_BUDGET && sums_stay &&
+      recheck_tile()) {
+    g_list_stats[0] += 1;
+    const int am = acc_mode(acc_kind, tb + a_bytes <= LDS_BUDGET);
+    const size_t tl = tb + ((am & AM_INLDS) ? a_bytes : 0);
+    return vec ? launch_tile_t<true, TX>(X, d, ldx, k, v, lab_out, acc, am,
+                                         base, nseg, tl, s, bnd)
+               : launch_tile_t<false, TX>(X, d, ldx, k, v, lab_out, acc, am,
+                                          base, nseg, tl, s, bnd);
+  }
+  g_list_stats[1] += 1;
   if (bnd) {
-    if (maxd != 32 || wave_all)
-      return fail(DKM_E_ARG, "list re-check: bounds need d <= 32");
     return vec ? launch_list_bnd_t<true, TX>(X, d, ldx, k, v, lab_out, acc,
                                              amode, base, nseg, lds, s, *bnd)
                : launch_list_bnd_t<false, TX>(X, d, ldx, k, v, lab_out, acc,

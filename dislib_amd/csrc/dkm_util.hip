@@ -802,4 +802,29 @@ int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
   return 0;
 }
 
+int dkm_list_stats(const void *ws, size_t ws_bytes, int64_t *out,
+                   int32_t *seg, int64_t seg_cap, void *stream) {
+  if (!ws || !out || (seg_cap > 0 && !seg) || seg_cap < 0)
+    return fail(DKM_E_ARG, "list_stats: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  dkm::list_launch_stats(out);
+  const int64_t nseg =
+      std::max<int64_t>(0, std::min<int64_t>({out[2], TL_SEGS, seg_cap}));
+  if (nseg == 0) return 0;
+  WsHeader h;
+  hipError_t e = hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess)
+    return fail((int)e, std::string("list_stats: ") + hipGetErrorString(e));
+  if (h.magic != WS_MAGIC) return fail(DKM_E_ARG, "list_stats: bad ws");
+  WsView v;
+  if (int r = ws_view(ws, ws_bytes, h.k, h.d, &v)) return r;
+  e = hipMemcpyAsync(seg, v.tcount, (size_t)nseg * 4, hipMemcpyDeviceToHost,
+                     s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess)
+    return fail((int)e, std::string("list_stats: ") + hipGetErrorString(e));
+  return 0;
+}
+
 }  // extern "C"

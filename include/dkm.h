@@ -603,6 +603,14 @@ int dkm_screen_counters(const void *ws, int64_t *out, void *stream);
  * samples that overflowed a list (found by the label scan).               */
 int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
                      void *stream);
+/* The list re-check's launches (host, syncs `stream`; diagnostics and the
+ * tests' A/B): out[0] launches of this process in the tile form
+ * (k_recheck_tile, d <= 32), out[1] in the lane form (k_recheck_list),
+ * out[2] the list segments of the last one (out has 3 entries); seg[i],
+ * i < min(out[2], seg_cap), the entries in segment i as the last screen
+ * launch on this workspace left them (seg may be NULL with seg_cap 0).     */
+int dkm_list_stats(const void *ws, size_t ws_bytes, int64_t *out,
+                   int32_t *seg, int64_t seg_cap, void *stream);
 
 /* Build flags of this library: 0 for a product build.  DKM_BUILD_TIMING_ONLY
  * when an object was compiled with an A/B timing probe that invalidates
