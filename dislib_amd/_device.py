@@ -434,6 +434,17 @@ def bounds_settled(ws):
     return int(out.value)
 
 
+def bounds_fused_stats(ws):
+    """(fused list-form kernels this process launched, bounds calls of this
+    workspace the fused form took, active rows of the workspace's last
+    bounds call or -1) (dkm_bounds_fused_stats)."""
+    so = _lib.lib()
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(so.dkm_bounds_fused_stats(ws.p, out, stream_ptr()),
+               "dkm_bounds_fused_stats")
+    return tuple(int(x) for x in out)
+
+
 def sorted_image_ok(dd, k):
     """Does the fit's auto mode on (k, d) run the single-product screen that
     takes a label-sorted image (dkm_x_image_sorted_ok)?"""

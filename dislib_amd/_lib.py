@@ -79,6 +79,7 @@ SIGNATURES = {
                                            _i32, _p, _p, _i32, _p]),
     "dkm_bounds_counters": (_i32, [_p, ctypes.POINTER(_i64), _p]),
     "dkm_bounds_settled": (_i32, [_p, ctypes.POINTER(_i64), _p]),
+    "dkm_bounds_fused_stats": (_i32, [_p, ctypes.POINTER(_i64), _p]),
     "dkm_label_sums_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,
                                   _p, _p]),
     "dkm_label_sums_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _sz,

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -808,10 +809,30 @@ struct BndArgs {
   int upd;                // 0: the image screen runs whatever *nact
   int vec;                // list form: rows are read in 16-B pieces (else
                           // element by element: d % 8 != 0 or unaligned X)
+  int fuse;               // a fused launch went before (it may have taken
+                          // the call: hdr->bnd_fused)
+  uint32_t fthresh;       // fused form iff the previous call's active rows
+                          // were at most this many
 };
-template <class TX, bool IMG, bool HINT = false, bool BND = false>
+//
+// FUSE (list form only, DESIGN.md 3.14 "The fused list form"): the bounds
+// pass and the list form in one launch.  Every wave streams its own 256-row
+// chunks of (ub, lb, label) -- k_bounds_pass's update, expression for
+// expression -- stages the rows it leaves active in LDS and screens them 32
+// at a time with the list form's step, the staged rows in place of list[..];
+// the next chunks' bounds and the next step's rows are in flight under the
+// MFMA chain, and the last step of a wave runs partially filled.  The
+// kernel runs when the previous bounds call left at most bnd.fthresh rows
+// active (hdr->bnd_last), says so in hdr->bnd_fused, and then finishes as a
+// list form whatever this call's count; k_bounds_pass and both unfused forms
+// are launched after it and return at once when it ran (the list form's
+// first thread still advances the counters, from the exact hdr->nactive).
+constexpr int BF_U = 2;                       // 256-row chunks per unit
+constexpr int BF_STAGE = 32 + 256 * BF_U;     // staged rows per wave (LDS)
+template <class TX, bool IMG, bool HINT = false, bool BND = false,
+          bool FUSE = false>
 __global__ void __launch_bounds__(SBW) __attribute__((
-    amdgpu_waves_per_eu(3)))
+    amdgpu_waves_per_eu(FUSE ? 2 : 3)))
     k_screen_w32(const TX *__restrict__ X, int64_t n, int d, int64_t ldx,
                  int k, WsView v, int32_t *__restrict__ lab_out, double *acc,
                  int amode, int64_t base, int use_list, XImage img,
@@ -819,23 +840,38 @@ __global__ void __launch_bounds__(SBW) __attribute__((
   constexpr int GB = 8;  // 32-centre blocks per packing group
   constexpr bool LIST = BND && !IMG;
   static_assert(!BND || HINT, "bounds come from the threshold pass");
+  static_assert(!FUSE || LIST, "the fused form is a list form");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   int64_t nl = n;  // rows to walk: n, or the list's length
   if constexpr (BND) {
-    const uint32_t na = bnd.upd ? *bnd.nact : 0u;
-    const bool listpath = bnd.upd && na <= bnd.thresh;
-    if constexpr (LIST) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        WsHeader *hd = v.hdr;
-        hd->bnd_calls += 1;
-        hd->bnd_active += na;
-        hd->bnd_skipped += (uint64_t)n - na;
-        hd->bnd_list_calls += listpath ? 1 : 0;
-      }
-      if (!listpath) return;
-      nl = na;
+    if constexpr (FUSE) {
+      // bnd_last: the previous call's active rows + 1 (0: none, or an init
+      // call); no kernel of a bounds call but the last reader writes it
+      const uint32_t pl = v.hdr->bnd_last;
+      const bool go = pl != 0 && pl - 1 <= bnd.fthresh;
+      if (blockIdx.x == 0 && threadIdx.x == 0) v.hdr->bnd_fused = go ? 1u : 0u;
+      if (!go) return;
     } else {
-      if (listpath) return;
+      const bool fused = bnd.fuse && v.hdr->bnd_fused != 0;
+      const uint32_t na = bnd.upd ? *bnd.nact : 0u;
+      const bool listpath = bnd.upd && (fused || na <= bnd.thresh);
+      if constexpr (LIST) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+          WsHeader *hd = v.hdr;
+          hd->bnd_calls += 1;
+          hd->bnd_active += na;
+          hd->bnd_skipped += (uint64_t)n - na;
+          hd->bnd_list_calls += listpath ? 1 : 0;
+          hd->bnd_fused_calls += fused ? 1 : 0;
+          hd->bnd_last = na + 1;
+        }
+        if (!listpath || fused) return;
+        nl = na;
+      } else {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && !bnd.upd)
+          v.hdr->bnd_last = 0;
+        if (listpath) return;
+      }
     }
   }
   const int nkb = (int)(kpad32(k) / 32);
@@ -872,6 +908,13 @@ __global__ void __launch_bounds__(SBW) __attribute__((
                        : v.cn32f[(p >> 5) * 32 + 16 * ((q >> 2) & 1) + g];
     }
   }
+  // FUSE: after the moved-row staging, every wave's stage of active rows,
+  // then the centres' drifts
+  int *stg0 = (int *)(pcn + (HINT ? kpad32(k) * 16 : 0)) +
+              (SBW / 64) * W32_MLB;
+  float *sdr = (float *)(stg0 + (SBW / 64) * BF_STAGE);
+  if constexpr (FUSE)
+    for (int e = threadIdx.x; e < k; e += SBW) sdr[e] = v.drift[e];
   __syncthreads();
 
   const int lane = threadIdx.x & 63, h = lane >> 5, r = lane & 31;
@@ -929,16 +972,24 @@ __global__ void __launch_bounds__(SBW) __attribute__((
                   (uint32_t)(16 * lpos);
   const bool two = d > 16;  // the second half holds features
   int rowid = -1;  // LIST: the sample of this lane's row r (-1 past the list)
+  // FUSE: this wave's staged active rows; the tile is stg[cnt .. cnt + take)
+  int *stg = stg0 + wid * BF_STAGE;
+  int cnt = 0, take = 0;  // wave-uniform
+  auto tile_row = [&](int64_t s0, int j) -> int {  // row j of the tile
+    if constexpr (FUSE)
+      return j < take ? stg[cnt + j] : -1;
+    else
+      return s0 + j < nl ? bnd.list[s0 + j] : -1;
+  };
   auto load_tile = [&](int64_t s0) {
     if constexpr (LIST) {
       // rows list[s0 ..]: 64-bit addresses (no common base), and only the
       // pieces that hold features (past d a piece could leave X)
-      rowid = s0 + r < nl ? bnd.list[s0 + r] : -1;
+      rowid = tile_row(s0, r);
       pv = rowid >= 0 ? lab_out[rowid] : -1;
 #pragma unroll
       for (int i = 0; i < IC; ++i) {
-        const int64_t pos = s0 + RI * i + lrow;
-        const int64_t ro = pos < nl ? (int64_t)bnd.list[pos] : -1;
+        const int64_t ro = (int64_t)tile_row(s0, RI * i + lrow);
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           raw[c][i] = txv{};
@@ -1003,14 +1054,103 @@ __global__ void __launch_bounds__(SBW) __attribute__((
       qpv = (int)__builtin_amdgcn_raw_buffer_load_b32(rl, r * 4, 0, 0);
     }
   };
+  // FUSE: the bounds stream.  Unit b0: BF_U chunks of 256 rows, four rows
+  // per lane in 16-B loads, held in registers from one screen step to the
+  // next; fill() takes units until a whole step is staged (or the rows end)
+  // and next_tile() takes the step's rows off the stage and loads them.
+  f32x4 pu[BF_U], pl[BF_U];
+  int4 pq[BF_U];
+  const int64_t bstride = (int64_t)gridDim.x * (SBW / 64) * 256 * BF_U;
+  int64_t b0 = wv * 256 * BF_U;
+  uint32_t nact = 0;  // this wave's active rows
+  auto bounds_load = [&]() {
+#pragma unroll
+    for (int u = 0; u < BF_U; ++u) {
+      const int64_t i0 = b0 + 256 * u + 4 * lane;
+      if (i0 + 3 < n) {
+        pu[u] = *(const f32x4 *)(bnd.ub + i0);
+        pl[u] = *(const f32x4 *)(bnd.lb + i0);
+        pq[u] = *(const int4 *)(lab_out + i0);
+      } else {
+        float a[4], b[4];
+        int q[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const bool in = i0 + c < n;
+          a[c] = in ? bnd.ub[i0 + c] : 0.f;
+          b[c] = in ? bnd.lb[i0 + c] : 1.f;
+          q[c] = in ? lab_out[i0 + c] : 0;
+        }
+        pu[u] = f32x4{a[0], a[1], a[2], a[3]};
+        pl[u] = f32x4{b[0], b[1], b[2], b[3]};
+        pq[u] = make_int4(q[0], q[1], q[2], q[3]);
+      }
+    }
+  };
+  auto fill = [&]() {
+    const float d1 = v.hdr->dmax1, d2 = v.hdr->dmax2;
+    const int im = v.hdr->dimax;
+    const bool bad = v.hdr->drift_bad != 0;
+    while (cnt < 32 && b0 < n) {
+#pragma unroll
+      for (int u = 0; u < BF_U; ++u) {
+        const int64_t i0 = b0 + 256 * u + 4 * lane;
+        float ux[4] = {pu[u].x, pu[u].y, pu[u].z, pu[u].w};
+        float lx[4] = {pl[u].x, pl[u].y, pl[u].z, pl[u].w};
+        const int lbv[4] = {pq[u].x, pq[u].y, pq[u].z, pq[u].w};
+        bool act[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {  // (k_bounds_pass's update)
+          const bool ok = !bad && lbv[c] >= 0 && lbv[c] < k;
+          const float down = lbv[c] == im ? d2 : d1;
+          ux[c] = ok ? (ux[c] + sdr[ok ? lbv[c] : 0]) * (1.0f + 0x1.0p-22f)
+                     : INFINITY;
+          lx[c] = fmaxf(lx[c] - down, 0.f) * (1.0f - 0x1.0p-22f);
+          act[c] = i0 + c < n && !(ux[c] < lx[c]);
+        }
+        if (i0 + 3 < n) {
+          *(f32x4 *)(bnd.ub + i0) = f32x4{ux[0], ux[1], ux[2], ux[3]};
+          *(f32x4 *)(bnd.lb + i0) = f32x4{lx[0], lx[1], lx[2], lx[3]};
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (i0 + c < n) {
+              bnd.ub[i0 + c] = ux[c];
+              bnd.lb[i0 + c] = lx[c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const uint64_t m = __ballot(act[c]);
+          if (act[c]) stg[cnt + lane_prefix(m)] = (int)(i0 + c);
+          cnt += __popcll(m);
+          nact += (uint32_t)__popcll(m);
+        }
+      }
+      b0 += bstride;
+      if (b0 < n) bounds_load();
+    }
+    wave_sync_w();  // the staged rows, before their readers
+  };
+  auto next_tile = [&]() {
+    fill();
+    take = min(cnt, 32);
+    cnt -= take;
+    if (take) load_tile(0);
+    return take != 0;
+  };
   int64_t s0 = base + wv * 32;
-  if (s0 < nl) {
+  bool more = false;  // FUSE: a tile is loaded
+  if constexpr (FUSE) {
+    if (b0 < n) bounds_load();
+    more = next_tile();
+  } else if (s0 < nl) {
     if constexpr (IMG)
       load_img(s0);
     else
       load_tile(s0);
   }
-  for (; s0 < nl; s0 += step) {
+  for (; FUSE ? more : s0 < nl; s0 += step) {
     bf16x8 xh[2], xl[2];
     float xx;
     int prv;
@@ -1091,7 +1231,10 @@ __global__ void __launch_bounds__(SBW) __attribute__((
       dst[192] = xl[1];
       if (h == 0) ((float *)img.xx)[s0 + r] = xx;
     }
-    if (!full_acc && s_next < nl) load_tile(s_next);
+    if constexpr (FUSE)
+      more = next_tile();
+    else if (!full_acc && s_next < nl)
+      load_tile(s_next);
     }  // !IMG
 
     float r1 = INFINITY, r2 = INFINITY;
@@ -1349,6 +1492,7 @@ __global__ void __launch_bounds__(SBW) __attribute__((
   if (lane == 0) {
     if (listing) v.tcount[seg] = tl_cnt;
     if (tl_over) atomicAdd(&v.hdr->qcount, (uint32_t)tl_over);
+    if (FUSE && nact) atomicAdd(&v.hdr->nactive, nact);
   }
   if (amode & AM_INLDS) {
     __syncthreads();
@@ -2434,9 +2578,11 @@ constexpr int BP_STAGE = 1024;
 __global__ void __launch_bounds__(256)
     k_bounds_pass(float *__restrict__ ub, float *__restrict__ lb,
                   const int32_t *__restrict__ lab, int64_t n, int k, WsView v,
-                  int32_t *__restrict__ list, uint32_t cap) {
+                  int32_t *__restrict__ list, uint32_t cap, int fuse) {
   __shared__ int stage[4][BP_STAGE];
   __shared__ float sdr[W32_HINT_KMAX];
+  // the fused list form went before and took the call (k_screen_w32, FUSE)
+  if (fuse && v.hdr->bnd_fused != 0) return;
   for (int e = threadIdx.x; e < k; e += 256) sdr[e] = v.drift[e];
   __syncthreads();
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -2528,6 +2674,17 @@ static bool bounds_settle() {
   return !(e && e[0] == '0' && !e[1]);
 }
 
+// DKM_BOUNDS_FUSED=0 in the environment (read at every call, for A/B runs):
+// no fused list form is launched, and every bounds call runs the bounds pass
+// and one of the two unfused forms
+static bool bounds_fused() {
+  const char *e = getenv("DKM_BOUNDS_FUSED");
+  return !(e && e[0] == '0' && !e[1]);
+}
+// fused launches of this process so far (dkm_bounds_fused_stats)
+static std::atomic<int64_t> g_fused_launches;
+int64_t bounds_fused_launches() { return g_fused_launches.load(); }
+
 template <class TX>
 static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
                              int k, const WsView &v, int32_t *lab_out,
@@ -2535,7 +2692,7 @@ static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
                              int use_list, hipStream_t s, int *nseg,
                              XImage img, bool build = false,
                              const BndArgs *bnd = nullptr,
-                             bool listform = false) {
+                             bool listform = false, bool fused = false) {
   // the image serves launches that need no sums from the raw rows; a build
   // launch (full sums, base 0) writes it instead
   const bool im = !build && img.tiles && img.kind == IMG_SPLIT &&
@@ -2554,10 +2711,13 @@ static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
     if (!hint) return 1;  // the threshold passes only
     lds += (size_t)(SBW / 64) * W32_MLB * 4;
   }
+  // the fused list form: the waves' stages of active rows and the drifts
+  if (fused) lds += (size_t)(SBW / 64) * BF_STAGE * 4 + (size_t)kpad32(k) * 4;
   // bounds: the moved-row-listing threshold passes only
   if (bnd && !(hint && (amode & AM_MLIST) && base == 0)) return 1;
   const void *kf =
-      bnd    ? (listform ? (const void *)k_screen_w32<TX, false, true, true>
+      fused  ? (const void *)k_screen_w32<TX, false, true, true, true>
+      : bnd  ? (listform ? (const void *)k_screen_w32<TX, false, true, true>
                          : (const void *)k_screen_w32<TX, true, true, true>)
       : hint ? (const void *)k_screen_w32<TX, true, true>
       : im   ? (const void *)k_screen_w32<TX, true>
@@ -2570,7 +2730,11 @@ static int launch_screen_w32(const TX *X, int64_t end, int d, int64_t ldx,
   const int64_t need = (rows + per_block - 1) / per_block;
   const unsigned g = (unsigned)std::max<int64_t>(1, std::min(need, cap));
   *nseg = (int)std::min<int64_t>((int64_t)g * (SBW / 64), TL_SEGS);
-  if (bnd && listform)
+  if (fused)
+    k_screen_w32<TX, false, true, true, true><<<g, SBW, lds, s>>>(
+        X, end, d, ldx, k, v, lab_out, acc, amode, base, use_list,
+        XImage{nullptr, nullptr, IMG_NONE}, 0, *bnd);
+  else if (bnd && listform)
     k_screen_w32<TX, false, true, true><<<g, SBW, lds, s>>>(
         X, end, d, ldx, k, v, lab_out, acc, amode, base, use_list,
         XImage{nullptr, nullptr, IMG_NONE}, 0, *bnd);
@@ -3069,21 +3233,39 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
         // the bounds pass lists the rows with !(u < l) in v.sitems; then the
         // list form and the image form of the screen, of which the device
         // count of active rows lets one run (an init call: the image form)
+        // (the fused list form first: it takes the call when the previous
+        // call left at most half the list form's share active)
+        const double frac = bounds_list_frac();
+        const bool fuse = !o.bnds->init && frac > 0.0 && bounds_fused();
         const BndArgs ba{o.bnds->ub, o.bnds->lb, v.sitems, &v.hdr->nactive,
-                         (uint32_t)bounds_list_cap(n, bounds_list_frac()),
+                         (uint32_t)bounds_list_cap(n, frac),
                          o.bnds->init ? 0 : 1,
-                         p.vec ? 1 : 0};
-        int ns2 = 0;
+                         p.vec ? 1 : 0,
+                         fuse ? 1 : 0,
+                         (uint32_t)bounds_list_cap(n, 0.5 * std::min(
+                                                          1.0, frac))};
+        int ns2 = 0, ns3 = 0;
         if (ba.upd) {
           if (hipMemsetAsync(&v.hdr->nactive, 0, 4, s) != hipSuccess ||
               hipMemsetAsync(v.tcount, 0, (size_t)TL_SEGS * 4, s) !=
                   hipSuccess)
             return fail(DKM_E_LAUNCH, "bounds: memset");
+          if (fuse) {
+            r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
+                                      AM_DELTA | AM_MLIST, base, p.fb,
+                                      p.use_list, s, &ns3, img, false, &ba,
+                                      true, true);
+            if (r == 1)
+              return fail(DKM_E_ARG, "bounds: the screens do not fit LDS");
+            if (r) return r;
+            g_fused_launches += 1;
+          }
           const unsigned gb = (unsigned)std::max<int64_t>(
               1, std::min<int64_t>((n + 1023) / 1024,
                                    (int64_t)dev_info().cus * 8));
           k_bounds_pass<<<gb, 256, 0, s>>>(o.bnds->ub, o.bnds->lb, lab_out, n,
-                                           k, v, v.sitems, ba.thresh);
+                                           k, v, v.sitems, ba.thresh,
+                                           ba.fuse);
           if ((r = check_launch("bounds pass"))) return r;
           r = launch_screen_w32<TX>(X, end, d, ldx, k, v, lab_out, acc,
                                     AM_DELTA | AM_MLIST, base, p.fb,
@@ -3097,7 +3279,7 @@ static int launch_screen(int prec, const TX *X, int64_t n, int d,
                                     false);
         if (r == 1)
           return fail(DKM_E_ARG, "bounds: the screens do not fit LDS");
-        nseg = std::max(nseg, ns2);
+        nseg = std::max({nseg, ns2, ns3});
         // the centres these bounds hold for: the next call's drift
         if (!r && hipMemcpyAsync(v.prevc, C, (size_t)k * d * 8,
                                  hipMemcpyDeviceToDevice, s) != hipSuccess)

@@ -102,11 +102,19 @@ struct WsHeader {
   int32_t dimax;        // the centre that drifted most
   uint32_t drift_bad;   // a drift was not finite: every row is active
   uint32_t nactive;     // rows the bounds pass of this call left active
-  uint32_t pad4;
+  uint32_t bnd_last;    // the last bounds call's nactive + 1 (0: none yet, or
+                        // an init call): the next call's choice of the fused
+                        // list form
   // ... and the counters of dkm_bounds_counters
   uint64_t bnd_calls, bnd_active, bnd_skipped, bnd_list_calls;
   // rows the exact re-check's fp32 stage gave bounds to (dkm_bounds_settled)
   uint64_t bnd_settled;
+  // bounds calls the fused list form took (dkm_bounds_fused_stats), and
+  // whether it took the call in flight (written by the fused launch, read by
+  // the unfused kernels launched after it)
+  uint64_t bnd_fused_calls;
+  uint32_t bnd_fused;
+  uint32_t pad5;
 };
 constexpr uint64_t WS_MAGIC = 0x444b4d5753303037ull;  // "DKMWS007"
 constexpr size_t WS_HDR = 256;
@@ -406,6 +414,9 @@ __host__ __device__ inline int64_t dpad64(int64_t d) { return (d + 63) / 64 * 64
 // the tile form (k_recheck_tile), out[1] in the lane form (k_recheck_list),
 // and out[2] the list segments of the last one (dkm_list_stats)
 void list_launch_stats(int64_t *out);
+// dkm_dense.hip: launches of the fused list form (k_screen_w32, FUSE) by this
+// process so far (dkm_bounds_fused_stats)
+int64_t bounds_fused_launches();
 
 size_t ws_bytes(int64_t k, int64_t d, int64_t n_queue);
 int64_t default_queue(int64_t k, int64_t d);

@@ -771,6 +771,23 @@ int dkm_bounds_settled(const void *ws, int64_t *n_settled, void *stream) {
   return 0;
 }
 
+int dkm_bounds_fused_stats(const void *ws, int64_t *out, void *stream) {
+  if (!ws || !out) return fail(DKM_E_ARG, "bounds_fused_stats: NULL");
+  WsHeader h;
+  hipError_t e = hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost,
+                                (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess)
+    return fail((int)e, std::string("bounds_fused_stats: ") +
+                            hipGetErrorString(e));
+  if (h.magic != WS_MAGIC)
+    return fail(DKM_E_ARG, "bounds_fused_stats: bad ws");
+  out[0] = dkm::bounds_fused_launches();
+  out[1] = (int64_t)h.bnd_fused_calls;
+  out[2] = (int64_t)h.bnd_last - 1;
+  return 0;
+}
+
 int dkm_screen_lists(const void *ws, size_t ws_bytes, int64_t *out,
                      void *stream) {
   if (!ws || !out) return fail(DKM_E_ARG, "screen_lists: NULL");

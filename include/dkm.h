@@ -295,6 +295,15 @@ int dkm_assign_delta_bounds_f32(const float *X, const void *image,
                                 void *stream);
 int dkm_bounds_counters(const void *ws, int64_t *out, void *stream);
 int dkm_bounds_settled(const void *ws, int64_t *n_settled, void *stream);
+/* The fused list form: an update call whose previous bounds
+ * call left at most half the list form's share of the rows active runs the
+ * bounds pass and the list form as one kernel (chosen on the device; same
+ * labels, bounds and counters).  DKM_BOUNDS_FUSED=0 in the environment, read
+ * at every call, launches no fused kernel.  out[0]: fused kernels launched by
+ * this process (host), out[1]: bounds calls of this workspace the fused form
+ * took (device), out[2]: the active rows of the workspace's last bounds call
+ * (-1: none, or an init call).  Host, syncs `stream`. */
+int dkm_bounds_fused_stats(const void *ws, int64_t *out, void *stream);
 
 /* acc[k*(d+1)] += [sums | counts] of the rows of X by labels (label < 0 or
  * >= k: skipped): the sums half of dkm_partial_sum for known labels.       */
