@@ -908,6 +908,83 @@ def fft_z(x, n, batch):
     return out
 
 
+class KppWorkspace:
+    """The device buffers of one k-means++ seeding run (dkm_kpp_*) with ``L``
+    trials per round and ``k`` centres: the trial-major distances ``dc``
+    (L, n), the running minima ``mind``, the 1024-row segment sums ``bsum``
+    and their scan, the eval blocks' ``partial`` potentials, the (L, d) trial
+    table with its row numbers, the uniforms ``U`` (k - 1, L) and the chosen
+    ``indices``.  ValueError when they would leave less than 4 GiB of HBM
+    free (the rule of sums="reference")."""
+
+    def __init__(self, dd, k, L, U):
+        t = torch()
+        so = _lib.lib()
+        n, d = dd.n, dd.d
+        nb = int(so.dkm_kpp_workspace_bytes(n, d, L))
+        if nb == 0:
+            raise _lib.DkmError("dkm_kpp_workspace_bytes: bad n/d/L")
+        nb += 8 * (U.size + k)
+        free = t.cuda.mem_get_info(dd.device)[0]
+        if nb + _IMAGE_HEADROOM > free:
+            raise ValueError(
+                "k-means++ with %d trials on %d samples needs %.2f GiB of "
+                "HBM, and %.2f GiB are free (4 GiB stay free); lower "
+                "n_local_trials" % (L, n, nb / 2.0 ** 30, free / 2.0 ** 30))
+        dev = dd.device
+        f64 = dict(dtype=t.float64, device=dev)
+        nseg = (n + 1023) // 1024
+        self.L = L
+        self.blocks = [int(so.dkm_kpp_blocks(n, d, 1)),
+                       int(so.dkm_kpp_blocks(n, d, L))]
+        self.dc = _alloc("kpp_dc", 8 * L * n, lambda: t.empty((L, n), **f64))
+        self.mind = t.empty(n, **f64)
+        self.bsum = t.empty(nseg, **f64)
+        self.bscan = t.empty(nseg, **f64)
+        self.partial = t.empty(max(self.blocks) * L, **f64)
+        self.trials = t.empty((L, d), **f64)
+        self.rows = t.zeros(L, dtype=t.int32, device=dev)
+        self.pot = t.zeros(1, **f64)
+        self.best = t.zeros(1, dtype=t.int32, device=dev)
+        self.indices = t.zeros(k, dtype=t.int64, device=dev)
+        self.U = t.from_numpy(np.ascontiguousarray(U)).to(dev) if U.size \
+            else None
+        preload(dev)
+
+
+def kpp_eval(dd, ws, L, first):
+    """Score the first ``L`` rows of the trial table against every sample."""
+    so = _lib.lib()
+    fn = so.dkm_kpp_eval_f32 if dd.dtype == np.float32 else so.dkm_kpp_eval_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(ws.trials), L,
+                  None if first else ptr(ws.mind), ptr(ws.dc),
+                  ws.dc.stride(0), ptr(ws.partial), stream_ptr()),
+               "dkm_kpp_eval")
+
+
+def kpp_commit(dd, ws, L, first, t_index):
+    """Choose the best of the ``L`` scored trials and commit it as centre
+    ``t_index``."""
+    so = _lib.lib()
+    _lib.check(so.dkm_kpp_commit(
+        dd.n, L, ptr(ws.dc), ws.dc.stride(0), ptr(ws.partial),
+        ws.blocks[0 if L == 1 else 1], ptr(ws.rows), int(first),
+        ptr(ws.mind), ptr(ws.bsum), ptr(ws.pot), ptr(ws.best),
+        ptr(ws.indices[t_index:]), stream_ptr()), "dkm_kpp_commit")
+
+
+def kpp_sample(dd, ws, L, round_index):
+    """Draw the trial rows of round ``round_index`` (1 .. k - 1) from the
+    uniforms ``U[round_index - 1]`` and gather them into the trial table."""
+    so = _lib.lib()
+    fn = so.dkm_kpp_sample_f32 if dd.dtype == np.float32 else \
+        so.dkm_kpp_sample_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(ws.mind),
+                  ptr(ws.bsum), ptr(ws.bscan), ptr(ws.pot),
+                  ptr(ws.U[round_index - 1]), L, ptr(ws.rows),
+                  ptr(ws.trials), stream_ptr()), "dkm_kpp_sample")
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

@@ -25,6 +25,7 @@ ALS_MAX_NF, ALS_CHUNK = 128, 16
 SVM_LINEAR, SVM_RBF, SVM_QMAX = 0, 1, 128
 RF_MAX_CLASSES, RF_MAX_SAMPLES, RF_LDS_MAX = 32, 1 << 24, 32768
 RF_AUTO, RF_LDS, RF_STREAM = 0, 1, 2
+KPP_MAX_TRIALS = 32
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -213,6 +214,19 @@ SIGNATURES = {
     "dkm_fft_workspace_bytes": (_sz, [_i64, _i64]),
     "dkm_fft_twiddles": (_i32, [_i64, _p]),
     "dkm_fft_z": (_i32, [_p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    # k-means++ seeding: trial scoring, choose + commit, the sampler
+    "dkm_kpp_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dkm_kpp_blocks": (_i64, [_i64, _i64, _i64]),
+    "dkm_kpp_eval_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64,
+                                _p, _p]),
+    "dkm_kpp_eval_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64,
+                                _p, _p]),
+    "dkm_kpp_commit": (_i32, [_i64, _i64, _p, _i64, _p, _i64, _p, _i32, _p,
+                              _p, _p, _p, _p, _p]),
+    "dkm_kpp_sample_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p,
+                                  _i64, _p, _p, _p]),
+    "dkm_kpp_sample_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p,
+                                  _i64, _p, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

@@ -1,5 +1,5 @@
 from dislib_amd.cluster.dbscan import DBSCAN
 from dislib_amd.cluster.gm import GaussianMixture
-from dislib_amd.cluster.kmeans import KMeans
+from dislib_amd.cluster.kmeans import KMeans, kmeans_plusplus
 
-__all__ = ['KMeans', 'GaussianMixture', 'DBSCAN']
+__all__ = ['KMeans', 'GaussianMixture', 'DBSCAN', 'kmeans_plusplus']

@@ -39,6 +39,11 @@ k (d + 1) fp64 per Subset of the whole Dataset stays in HBM (a ValueError
 when that would leave less than 4 GiB free).  CSR data is not supported in
 this mode (NotImplementedError); ``arity < 2`` with more than one Subset,
 with which the reference never terminates, is a ValueError.
+
+``init="k-means++"`` (keyword-only; the default ``"random"`` is the
+reference's rule above, bit for bit) seeds the fit with
+:func:`kmeans_plusplus`: sklearn's greedy D^2 seeding, computed on the GPU
+(dkm_kpp_*).  Dense Datasets on one rank only.
 """
 import os
 
@@ -51,6 +56,7 @@ _MODES = {"auto": _lib.MODE_AUTO, "exact": _lib.MODE_EXACT,
           "screen32": _lib.MODE_SCREEN32, "bf16x3": _lib.MODE_BF16X3,
           "bf16": _lib.MODE_BF16}
 _SUMS = ("fast", "reference")
+_INITS = ("random", "k-means++")
 
 
 def _init_centers(n_features, sparse, n_clusters, random_state):
@@ -62,13 +68,79 @@ def _init_centers(n_features, sparse, n_clusters, random_state):
     return centers
 
 
+def kmeans_plusplus(dataset, n_clusters, *, random_state=None,
+                    n_local_trials=None, device=None):
+    """k-means++ seeding of ``dataset`` (dense) on the GPU: sklearn's greedy
+    rule.  Returns ``(centers, indices)``: the chosen rows widened to a
+    (k, d) fp64 array, and their global row numbers in Dataset order (int64).
+
+    With ``rs = np.random.RandomState(random_state)`` and ``L =
+    n_local_trials or 2 + int(np.log(k))``: the first row is
+    ``rs.randint(n)``; ``U = rs.uniform(size=(k - 1, L))`` is drawn once;
+    round t takes the trial rows ``min(searchsorted(cumsum(mind), U[t - 1] *
+    pot), n - 1)``, scores each by the potential ``sum_i min(mind[i], |x_i -
+    x_trial|^2)`` and keeps the first minimum.  Distances are direct sums of
+    squared differences in fp64.  The k - 1 rounds are enqueued back to back;
+    one scalar (the first potential) is read before them and the indices
+    after them.  A potential of 0 (fewer distinct rows than k) takes row 0.
+    """
+    if isinstance(random_state, np.random.RandomState):
+        raise TypeError("random_state must be an int or None "
+                        "(np.random.RandomState(random_state) is drawn from)")
+    if dataset.sparse:
+        raise NotImplementedError(
+            "kmeans_plusplus takes a dense Dataset: CSR samples are not "
+            "supported")
+    if _shard.active():
+        raise NotImplementedError(
+            "kmeans_plusplus runs on one rank: a torch.distributed world "
+            "larger than 1 is not supported")
+    k = int(n_clusters)
+    if k < 1:
+        raise ValueError("n_clusters must be at least 1, got %d" % k)
+    n = sum(int(s.samples.shape[0]) for s in dataset)
+    if n == 0:
+        raise ValueError("kmeans_plusplus of an empty Dataset")
+    if k > n:
+        raise ValueError("n_clusters=%d exceeds the %d samples" % (k, n))
+    L = 2 + int(np.log(k)) if n_local_trials is None else n_local_trials
+    if L != int(L) or not 1 <= L <= _lib.KPP_MAX_TRIALS:
+        raise ValueError("n_local_trials must be in 1..%d, got %r"
+                         % (_lib.KPP_MAX_TRIALS, n_local_trials))
+    L = int(L)
+    _lib.lib()                          # no GPU / no libdkm: raise here
+    from .._device import KppWorkspace, kpp_commit, kpp_eval, kpp_sample, on
+    rs = np.random.RandomState(random_state)
+    i0 = int(rs.randint(n))
+    U = rs.uniform(size=(k - 1, L))
+    dd = dataset._device_data(device)
+    with on(dd.device):
+        ws = KppWorkspace(dd, k, L, U)
+        ws.rows[:1] = i0
+        ws.trials[0] = dd.X[i0]
+        kpp_eval(dd, ws, 1, True)
+        kpp_commit(dd, ws, 1, True, 0)
+        if not np.isfinite(ws.pot.item()):
+            raise ValueError("kmeans_plusplus: non-finite samples")
+        for t in range(1, k):
+            kpp_sample(dd, ws, L, t)
+            kpp_eval(dd, ws, L, False)
+            kpp_commit(dd, ws, L, False, t)
+        idx = ws.indices
+        centers = dd.X[idx].double().cpu().numpy()
+        indices = idx.cpu().numpy()
+    return centers, indices
+
+
 class KMeans:
     """Perform K-means clustering (Lloyd) on MI355X.
 
     Parameters match ``dislib.cluster.KMeans``; ``mode`` and ``device`` are
     keyword-only extensions, ``sums`` too ("fast": the default order;
     "reference": the reference's order, bit-identical centres -- see the
-    module docstring).  Under ``torch.distributed`` with more than one
+    module docstring), and ``init`` ("random": the reference's uniform
+    centres; "k-means++": :func:`kmeans_plusplus`, whose row numbers are then
+    in ``init_indices_``).  Under ``torch.distributed`` with more than one
     rank, each rank passes its own shard Dataset (see
     :func:`dislib_amd.shard_dataset`) and the per-iteration [sums | counts]
     are all-reduced (RCCL).
@@ -76,7 +148,7 @@ class KMeans:
 
     def __init__(self, n_clusters=8, max_iter=10, tol=1e-4, arity=50,
                  random_state=None, verbose=False, *, mode="auto",
-                 device=None, sums="fast"):
+                 device=None, sums="fast", init="random"):
         self._n_clusters = n_clusters
         self._max_iter = max_iter
         self._tol = tol
@@ -91,6 +163,10 @@ class KMeans:
         if sums not in _SUMS:
             raise ValueError("sums must be one of %s" % sorted(_SUMS))
         self._sums = sums
+        if init not in _INITS:
+            raise ValueError("init must be one of %s" % sorted(_INITS))
+        self._init = init
+        self.init_indices_ = None
         self._device = device
         self._rechecked = 0
 
@@ -137,14 +213,22 @@ class KMeans:
         if isinstance(self._random_state, np.random.RandomState):
             raise TypeError("random_state must be an int or None "
                             "(np.random.seed, as in the reference)")
-        _lib.lib()                          # no GPU / no libdkm: raise here
         sparse = dataset.sparse
+        self.init_indices_ = None
+        if self._init == "k-means++":
+            # refuses sparse samples and a distributed world before the
+            # library is touched
+            centers, self.init_indices_ = kmeans_plusplus(
+                dataset, self._n_clusters, random_state=self._random_state,
+                device=self._device)
+        _lib.lib()                          # no GPU / no libdkm: raise here
         if sparse and self._sums == "reference":
             raise NotImplementedError(
                 "sums='reference' takes dense samples: the reference's sparse "
                 "partials are scipy CSR sums with their own structure rules")
-        centers = _init_centers(dataset.n_features, sparse, self._n_clusters,
-                                self._random_state)
+        if self._init == "random":
+            centers = _init_centers(dataset.n_features, sparse,
+                                    self._n_clusters, self._random_state)
         state = _Lloyd(dataset, centers.toarray() if sparse else centers,
                        self._tol, set_labels, self._mode, self._device,
                        broadcast_init=self._random_state is None,

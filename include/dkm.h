@@ -997,6 +997,60 @@ int dkm_fft_z(const void *in, void *out, int64_t n, int64_t batch,
               const void *twiddles, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
+ * k-means++ seeding (KMeans(init="k-means++")): sklearn's
+ * greedy D^2 rule on dense rows, fp64 arithmetic (fp32 rows are widened in
+ * the loads), distances as sum_j (x_j - c_j)^2.  1 <= n < 2^31, d >= 1,
+ * ldx >= d, 1 <= L <= DKM_KPP_MAX_TRIALS trials per round.  Every entry is
+ * stream-ordered and asynchronous, uses no floating-point atomic and gives
+ * the same bits from run to run; DKM_E_ARG for a bad shape or pointer,
+ * before any device work.  A round is sample, eval, commit.
+ * --------------------------------------------------------------------- */
+#define DKM_KPP_MAX_TRIALS 32
+
+/* Bytes of the buffers of one seeding run with L trials per round: dc
+ * (L x n), mind (n), bsum and bscan (ceil(n / 1024) each), partial, the
+ * (L, d) trial table, the L rows and the scalars.  0 for a bad shape. */
+size_t dkm_kpp_workspace_bytes(int64_t n, int64_t d, int64_t L);
+
+/* HOST function: the blocks dkm_kpp_eval_* launches for (n, d, L), which is
+ * the number of rows of `partial` it writes.  0 for a bad shape. */
+int64_t dkm_kpp_blocks(int64_t n, int64_t d, int64_t L);
+
+/* dc[l * ldc + i] <- |x_i - trials[l]|^2 for the L rows of the (L, d) fp64
+ * table `trials` (ldc >= n), and partial[b * L + l] <- block b's sum over its
+ * rows of min(mind[i], dc[l][i]); mind == NULL (the first centre): the sum of
+ * dc[l][i] itself.  One read of X scores every trial. */
+int dkm_kpp_eval_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *trials, int64_t L, const double *mind,
+                     double *dc, int64_t ldc, double *partial, void *stream);
+int dkm_kpp_eval_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *trials, int64_t L, const double *mind,
+                     double *dc, int64_t ldc, double *partial, void *stream);
+
+/* Sums the `nblocks` rows of `partial` in a fixed order, takes the first
+ * minimum over the L trials and writes best[0] (the trial), pot[0] (its
+ * potential) and index_out[0] = rows[best]; then mind[i] <- fmin(mind[i],
+ * dc[best][i]) (first != 0: dc[best][i], mind is not read) and bsum[s] <- the
+ * sum of the new mind over rows [1024 s, 1024 s + 1024). */
+int dkm_kpp_commit(int64_t n, int64_t L, const double *dc, int64_t ldc,
+                   const double *partial, int64_t nblocks, const int32_t *rows,
+                   int first, double *mind, double *bsum, double *pot,
+                   int32_t *best, int64_t *index_out, void *stream);
+
+/* rows[l] <- min(searchsorted(cumsum(mind), u[l] * pot[0], side='left'),
+ * n - 1), l < L, by a search over the inclusive scan of bsum (written to
+ * bscan, ceil(n / 1024) values) and a scan inside the segment found; and
+ * trials[l] <- row rows[l] of X, widened.  u and pot are device pointers. */
+int dkm_kpp_sample_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                       const double *mind, const double *bsum, double *bscan,
+                       const double *pot, const double *u, int64_t L,
+                       int32_t *rows, double *trials, void *stream);
+int dkm_kpp_sample_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                       const double *mind, const double *bsum, double *bscan,
+                       const double *pot, const double *u, int64_t L,
+                       int32_t *rows, double *trials, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
