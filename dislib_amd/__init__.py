@@ -18,22 +18,24 @@ from dislib_amd._shard import shard_dataset, shard_range  # noqa: E402,F401
 def install_as_dislib():
     """Alias ``dislib``, ``dislib.cluster``, ``dislib.data``,
     ``dislib.neighbors``, ``dislib.preprocessing``,
-    ``dislib.recommendation`` and ``dislib.fft`` to this package (the
-    k-means path, its data containers, the kNN reuse of its distance
-    primitive, the StandardScaler, ALS and the FFT)."""
+    ``dislib.recommendation``, ``dislib.fft`` and ``dislib.decomposition`` to
+    this package (the k-means path, its data containers, the kNN reuse of its
+    distance primitive, the StandardScaler, ALS, the FFT and PCA)."""
     import types
-    from dislib_amd import (cluster, data, fft, neighbors, preprocessing,
-                            recommendation)
+    from dislib_amd import (cluster, data, decomposition, fft, neighbors,
+                            preprocessing, recommendation)
     pkg = types.ModuleType("dislib")
     pkg.__path__ = []
     pkg.name = "dislib"
     pkg.cluster = cluster
     pkg.data = data
+    pkg.decomposition = decomposition
     pkg.fft = fft
     pkg.neighbors = neighbors
     pkg.preprocessing = preprocessing
     pkg.recommendation = recommendation
     sys.modules["dislib"] = pkg
+    sys.modules["dislib.decomposition"] = decomposition
     sys.modules["dislib.fft"] = fft
     sys.modules["dislib.preprocessing"] = preprocessing
     sys.modules["dislib.recommendation"] = recommendation

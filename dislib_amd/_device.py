@@ -985,6 +985,92 @@ def kpp_sample(dd, ws, L, round_index):
                   ptr(ws.trials), stream_ptr()), "dkm_kpp_sample")
 
 
+# ---------------------------------------------------------------------------
+# PCA (dkm_pca.hip)
+# ---------------------------------------------------------------------------
+# the plan of dkm_pca.hip restated, for the tests to name the branch a shape
+# reaches: columns of a macro tile of G, rows of a chunk (at least), rows the
+# pivot is the mean of (at most), the size the partials are capped at (about)
+PCA_TILE = 64
+PCA_CHUNK_ROWS = 512
+PCA_PIVOT_ROWS = 1024
+PCA_WORKSPACE = 64 << 20
+
+
+def pca_pairs(d):
+    """64 x 64 tiles of the (d + 1)^2 Gram matrix on or above the diagonal."""
+    p = (d + 1 + PCA_TILE - 1) // PCA_TILE
+    return p * (p + 1) // 2
+
+
+def pca_chunks(n, d):
+    """Row chunks of dkm_pca_gram_*: capped so that the partials (32 KiB per
+    chunk and tile) stay within about PCA_WORKSPACE -- but never below 8."""
+    cap = max(8, PCA_WORKSPACE // (pca_pairs(d) * PCA_TILE * PCA_TILE * 8))
+    return max(1, min((n + PCA_CHUNK_ROWS - 1) // PCA_CHUNK_ROWS, cap))
+
+
+def _pca_headroom(nb, what, dd):
+    free = torch().cuda.mem_get_info(dd.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        raise ValueError(
+            "PCA on %d x %d samples: %s needs %.2f GiB of HBM, and %.2f GiB "
+            "are free (4 GiB stay free)" % (dd.n, dd.d, what, nb / 2.0 ** 30,
+                                            free / 2.0 ** 30))
+
+
+def pca_workspace(dd):
+    """The workspace of :func:`pca_gram` for ``dd``; ValueError when it would
+    leave less than 4 GiB of HBM free."""
+    t = torch()
+    nb = int(_lib.lib().dkm_pca_workspace_bytes(dd.n, dd.d))
+    if nb == 0:
+        raise _lib.DkmError("dkm_pca_workspace_bytes: bad n/d")
+    _pca_headroom(nb, "the Gram partials", dd)
+    return _alloc("pca", nb, lambda: t.empty(nb, dtype=t.uint8,
+                                             device=dd.device))
+
+
+def pca_pivot(dd):
+    """The fp64 mean of the first min(n, PCA_PIVOT_ROWS) rows (device)."""
+    t = torch()
+    return dd.X[:PCA_PIVOT_ROWS, :dd.d].to(t.float64).mean(dim=0).contiguous()
+
+
+def pca_gram(dd, pivot, ws=None):
+    """The (d + 1, d + 1) fp64 device matrix G = sum of a^T a over the rows
+    a = [x - pivot | 1] of ``dd`` (``pivot``: device fp64[d]), in one read of
+    X (dkm_pca_gram_*)."""
+    t = torch()
+    so = _lib.lib()
+    if ws is None:
+        ws = pca_workspace(dd)
+    G = t.empty((dd.d + 1, dd.d + 1), dtype=t.float64, device=dd.device)
+    fn = so.dkm_pca_gram_f32 if dd.dtype == np.float32 else so.dkm_pca_gram_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(pivot), ptr(ws),
+                  ws.numel(), ptr(G), stream_ptr()), "dkm_pca_gram")
+    return G
+
+
+def pca_project(dd, mean, V):
+    """The (n, c) fp64 device matrix (X - mean) V^T for the device fp64
+    ``mean`` (d) and ``V`` (c, d) (dkm_pca_project_*); ValueError when it would
+    leave less than 4 GiB of HBM free."""
+    t = torch()
+    so = _lib.lib()
+    V = V.contiguous()
+    c = int(V.shape[0])
+    _pca_headroom(8 * dd.n * c, "the projected samples", dd)
+    Y = _alloc("pca_y", 8 * dd.n * c, lambda: t.empty(
+        (dd.n, c), dtype=t.float64, device=dd.device))
+    fn = so.dkm_pca_project_f32 if dd.dtype == np.float32 else \
+        so.dkm_pca_project_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(mean),
+                  ptr(V), c, ptr(Y), Y.stride(0), stream_ptr()),
+               "dkm_pca_project")
+    return Y
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

@@ -39,6 +39,7 @@ int preload_svm();
 int preload_rf();
 int preload_fft();
 int preload_kpp();
+int preload_pca();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -72,6 +73,7 @@ int tu_flags_svm();
 int tu_flags_rf();
 int tu_flags_fft();
 int tu_flags_kpp();
+int tu_flags_pca();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

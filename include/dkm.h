@@ -1051,6 +1051,43 @@ int dkm_kpp_sample_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                        int32_t *rows, double *trials, void *stream);
 
 /* ------------------------------------------------------------------------
+ * PCA (dislib_amd.decomposition.PCA) on dense rows: fp64
+ * arithmetic on the f64 MFMA (fp32 rows are widened in the loads), n >= 1,
+ * 1 <= d <= DKM_PCA_MAX_D, ldx >= d.  Every entry but the first is
+ * stream-ordered and asynchronous, uses no floating-point atomic and gives
+ * the same bits from run to run; DKM_E_ARG for a bad shape or pointer and
+ * DKM_E_WORKSPACE for a short workspace, before any device work.
+ * --------------------------------------------------------------------- */
+#define DKM_PCA_MAX_D 4096
+
+/* HOST function: bytes of dkm_pca_gram_*'s workspace, 32 KiB per (row chunk,
+ * 64 x 64 tile of G on or above the diagonal); the chunks are a function of
+ * (n, d).  0 for a bad shape. */
+size_t dkm_pca_workspace_bytes(int64_t n, int64_t d);
+
+/* G ((d + 1) x (d + 1), row-major, exactly symmetric) <- sum over the rows of
+ * a^T a with a = [x - pivot | 1]: G[:d,:d] is the scatter about `pivot` (d
+ * fp64 device values, any finite vector; one near the mean avoids the
+ * cancellation in G[:d,:d] - s s^T / n), column d is s = sum(x - pivot) and
+ * G[d][d] == n.  One read of X. */
+int dkm_pca_gram_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *pivot, void *ws, size_t ws_bytes, double *G,
+                     void *stream);
+int dkm_pca_gram_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                     const double *pivot, void *ws, size_t ws_bytes, double *G,
+                     void *stream);
+
+/* Y[i][j] (ldy >= c) <- sum_f (x_if - mean[f]) V[j][f] for the c rows of the
+ * (c, d) fp64 device matrix V, 1 <= c <= DKM_PCA_MAX_D: the mean is
+ * subtracted from every element before the product. */
+int dkm_pca_project_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                        const double *mean, const double *V, int64_t c,
+                        double *Y, int64_t ldy, void *stream);
+int dkm_pca_project_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                        const double *mean, const double *V, int64_t c,
+                        double *Y, int64_t ldy, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
