@@ -18,12 +18,13 @@ from dislib_amd._shard import shard_dataset, shard_range  # noqa: E402,F401
 def install_as_dislib():
     """Alias ``dislib``, ``dislib.cluster``, ``dislib.data``,
     ``dislib.neighbors``, ``dislib.preprocessing``,
-    ``dislib.recommendation``, ``dislib.fft`` and ``dislib.decomposition`` to
-    this package (the k-means path, its data containers, the kNN reuse of its
-    distance primitive, the StandardScaler, ALS, the FFT and PCA)."""
+    ``dislib.recommendation``, ``dislib.fft``, ``dislib.decomposition`` and
+    ``dislib.regression`` to this package (the k-means path, its data
+    containers, the kNN reuse of its distance primitive, the StandardScaler,
+    ALS, the FFT, PCA and LinearRegression)."""
     import types
     from dislib_amd import (cluster, data, decomposition, fft, neighbors,
-                            preprocessing, recommendation)
+                            preprocessing, recommendation, regression)
     pkg = types.ModuleType("dislib")
     pkg.__path__ = []
     pkg.name = "dislib"
@@ -34,11 +35,13 @@ def install_as_dislib():
     pkg.neighbors = neighbors
     pkg.preprocessing = preprocessing
     pkg.recommendation = recommendation
+    pkg.regression = regression
     sys.modules["dislib"] = pkg
     sys.modules["dislib.decomposition"] = decomposition
     sys.modules["dislib.fft"] = fft
     sys.modules["dislib.preprocessing"] = preprocessing
     sys.modules["dislib.recommendation"] = recommendation
+    sys.modules["dislib.regression"] = regression
     sys.modules["dislib.neighbors"] = neighbors
     sys.modules["dislib.cluster"] = cluster
     sys.modules["dislib.data"] = data

@@ -1071,6 +1071,60 @@ def pca_project(dd, mean, V):
     return Y
 
 
+# ---------------------------------------------------------------------------
+# Tall-skinny QR (dkm_qr.hip)
+# ---------------------------------------------------------------------------
+# the plan of dkm_qr.hip restated, for the tests to name the branch a shape
+# reaches: rows of a tile, rows of a range (at least), ranges (at most), the
+# Rs one merge workgroup stacks
+TSQR_TILE = 64
+TSQR_RANGE_ROWS = 2048
+TSQR_MAX_RANGES = 512
+TSQR_FAN = 8
+
+
+def tsqr_ranges(n):
+    """Row ranges (workgroups) of dkm_tsqr_*'s panel pass."""
+    return max(1, min((n + TSQR_RANGE_ROWS - 1) // TSQR_RANGE_ROWS,
+                      TSQR_MAX_RANGES))
+
+
+def tsqr_workspace(dd, w):
+    """The workspace of :func:`tsqr` for ``dd`` and ``w`` columns; ValueError
+    when it would leave less than 4 GiB of HBM free."""
+    t = torch()
+    nb = int(_lib.lib().dkm_tsqr_workspace_bytes(dd.n, w))
+    if nb == 0:
+        raise _lib.DkmError("dkm_tsqr_workspace_bytes: bad n/w")
+    free = t.cuda.mem_get_info(dd.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        raise ValueError(
+            "LinearRegression on %d x %d samples: the range factors need "
+            "%.2f GiB of HBM, and %.2f GiB are free (4 GiB stay free)"
+            % (dd.n, dd.d, nb / 2.0 ** 30, free / 2.0 ** 30))
+    return _alloc("tsqr", nb, lambda: t.empty(nb, dtype=t.uint8,
+                                              device=dd.device))
+
+
+def tsqr(dd, y, ones, ws=None):
+    """The (w, w) fp64 device matrix R, upper triangular with a non-negative
+    diagonal, of A = [1 | X | y] (``ones``) or [X | y]: A^T A = R^T R, in one
+    read of X (dkm_tsqr_*).  ``y``: device fp64[n]."""
+    t = torch()
+    so = _lib.lib()
+    w = dd.d + 1 + int(bool(ones))
+    if y.dtype != t.float64 or y.numel() != dd.n or not y.is_contiguous():
+        raise ValueError("tsqr: y is one contiguous fp64 value per sample")
+    if ws is None:
+        ws = tsqr_workspace(dd, w)
+    R = t.empty((w, w), dtype=t.float64, device=dd.device)
+    fn = so.dkm_tsqr_f32 if dd.dtype == np.float32 else so.dkm_tsqr_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(y),
+                  int(bool(ones)), ptr(ws), ws.numel(), ptr(R), stream_ptr()),
+               "dkm_tsqr")
+    return R
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

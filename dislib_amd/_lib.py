@@ -27,6 +27,7 @@ RF_MAX_CLASSES, RF_MAX_SAMPLES, RF_LDS_MAX = 32, 1 << 24, 32768
 RF_AUTO, RF_LDS, RF_STREAM = 0, 1, 2
 KPP_MAX_TRIALS = 32
 PCA_MAX_D = 4096
+TSQR_MAX_W = 128
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -236,6 +237,10 @@ SIGNATURES = {
                                    _i64, _p]),
     "dkm_pca_project_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64, _p,
                                    _i64, _p]),
+    # LinearRegression: the R factor of [1 | X | y] by a tall-skinny QR
+    "dkm_tsqr_workspace_bytes": (_sz, [_i64, _i64]),
+    "dkm_tsqr_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _p, _sz, _p, _p]),
+    "dkm_tsqr_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _p, _sz, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

@@ -40,6 +40,7 @@ int preload_rf();
 int preload_fft();
 int preload_kpp();
 int preload_pca();
+int preload_qr();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -74,6 +75,7 @@ int tu_flags_rf();
 int tu_flags_fft();
 int tu_flags_kpp();
 int tu_flags_pca();
+int tu_flags_qr();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

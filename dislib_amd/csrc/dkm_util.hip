@@ -641,7 +641,8 @@ int dkm_preload(void) {
          preload_gemm() + preload_sums() + preload_neighbors() +
          preload_ordered() + preload_scale() + preload_gm() +
          preload_dbscan() + preload_als() + preload_svm() + preload_rf() +
-         preload_fft() + preload_kpp() + preload_pca();
+         preload_fft() + preload_kpp() + preload_pca() +
+         preload_qr();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

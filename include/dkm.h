@@ -1088,6 +1088,35 @@ int dkm_pca_project_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                         double *Y, int64_t ldy, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Tall-skinny QR (dislib_amd.regression.LinearRegression)
+ * of the implicit matrix A = [1 | X | y] (ones != 0) or [X | y] of n dense
+ * rows: w = d + 1 + ones <= DKM_TSQR_MAX_W columns, n >= 1, d >= 1,
+ * ldx >= d, y an fp64 device vector of n values.  fp64 Householder
+ * arithmetic, the trailing updates on the f64 MFMA (fp32 rows are widened in
+ * the loads); one read of X; the ones and y columns are assembled in the
+ * loads.  Stream-ordered and asynchronous, no floating-point atomic, the
+ * same bits from run to run; DKM_E_ARG for a bad shape or pointer and
+ * DKM_E_WORKSPACE for a short workspace, before any device work.  Squares
+ * are not scaled: entries beyond about 1e150 overflow to a non-finite R.
+ * --------------------------------------------------------------------- */
+#define DKM_TSQR_MAX_W 128
+
+/* HOST function: bytes of dkm_tsqr_*'s workspace (the row ranges' R factors,
+ * padded to a multiple of 16 columns; the ranges are a function of n).  0 for
+ * a bad shape. */
+size_t dkm_tsqr_workspace_bytes(int64_t n, int64_t w);
+
+/* R (w x w, row-major) <- the upper-triangular factor of A, A^T A = R^T R:
+ * zeros below the diagonal, the diagonal non-negative (unique for full-rank
+ * A).  With ones, R[0][:] = sqrt(n) [1, mean(X), mean(y)]. */
+int dkm_tsqr_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                 const double *y, int ones, void *ws, size_t ws_bytes,
+                 double *R, void *stream);
+int dkm_tsqr_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                 const double *y, int ones, void *ws, size_t ws_bytes,
+                 double *R, void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
