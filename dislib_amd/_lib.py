@@ -25,6 +25,7 @@ ALS_MAX_NF, ALS_CHUNK = 128, 16
 SVM_LINEAR, SVM_RBF, SVM_QMAX = 0, 1, 128
 RF_MAX_CLASSES, RF_MAX_SAMPLES, RF_LDS_MAX = 32, 1 << 24, 32768
 RF_AUTO, RF_LDS, RF_STREAM = 0, 1, 2
+RFR_LDS_MAX = 16384
 KPP_MAX_TRIALS = 32
 PCA_MAX_D = 4096
 TSQR_MAX_W = 128
@@ -212,6 +213,14 @@ SIGNATURES = {
                                   _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     "dkm_rf_predict_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
                                   _p, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    # RandomForestRegressor: split search, node statistics, predict
+    "dkm_rfr_split": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64,
+                             _i64, _i32, _p, _p, _p]),
+    "dkm_rfr_node_stats": (_i32, [_p, _i64, _p, _p, _i64, _p, _p]),
+    "dkm_rfr_predict_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
+                                   _p, _p, _p]),
+    "dkm_rfr_predict_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p,
+                                   _p, _p, _p]),
     # fft: workspace size, the host twiddle table, the batched transform
     "dkm_fft_workspace_bytes": (_sz, [_i64, _i64]),
     "dkm_fft_twiddles": (_i32, [_i64, _p]),

@@ -41,6 +41,7 @@ int preload_fft();
 int preload_kpp();
 int preload_pca();
 int preload_qr();
+int preload_rfr();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -76,6 +77,7 @@ int tu_flags_fft();
 int tu_flags_kpp();
 int tu_flags_pca();
 int tu_flags_qr();
+int tu_flags_rfr();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

@@ -1,3 +1,4 @@
+from dislib_amd.regression.forest import RandomForestRegressor
 from dislib_amd.regression.linear import LinearRegression
 
-__all__ = ['LinearRegression']
+__all__ = ['LinearRegression', 'RandomForestRegressor']

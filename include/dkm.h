@@ -971,6 +971,47 @@ int dkm_rf_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                        void *stream);
 
 /* ------------------------------------------------------------------------
+ * RandomForestRegressor: the regression forest on the
+ * classifier's tables (rank, order, members, node_of, weight, nodes, pairs as
+ * above; dkm_rf_best and dkm_rf_partition serve it with C = 1 and zero codes).
+ * y[n]: the fp64 targets.  Sums are formed in a fixed order that depends on
+ * the node's size and the regime only: identical from run to run; the two
+ * regimes agree where every sum is exact (integer-valued targets).
+ * --------------------------------------------------------------------- */
+
+/* Largest node of the LDS regime: a 64-bit key (rank, position) per member,
+ * 128 KiB, next to the scan's and the reduction's scratch in the 160 KiB of
+ * LDS; the largest power of two that fits, not a measured optimum. */
+#define DKM_RFR_LDS_MAX 16384
+/* As dkm_rf_split, with the score -(SL^2 / |L| + SR^2 / |R|) of the left and
+ * right target sums (SR = nsum[node] - SL, every fp64 operation rounded on its
+ * own); nsum[i]: node i's target sum.  mode: DKM_RF_AUTO / _LDS / _STREAM
+ * with DKM_RFR_LDS_MAX as the bound. */
+int dkm_rfr_split(const int32_t *rank, const int32_t *order, int64_t n,
+                  const double *y, const int32_t *members,
+                  const int32_t *node_of, const int32_t *weight,
+                  const int32_t *nodes, const double *nsum,
+                  const int32_t *pairs, int64_t n_pairs, int64_t max_size,
+                  int mode, double *score, int32_t *cut, void *stream);
+/* stats[i] = {sum, min, max} of the targets of members[tree][start .. start +
+ * size) for nodes[i] = {tree, start, size, any}; {0, +inf, -inf} for size 0. */
+int dkm_rfr_node_stats(const double *y, int64_t n, const int32_t *members,
+                       const int32_t *nodes, int64_t n_nodes, double *stats,
+                       void *stream);
+/* out[r] <- the sum over the T trees, in tree order, of leaf[the leaf of row
+ * r], divided by T; the trees as dkm_rf_predict_* takes them. */
+int dkm_rfr_predict_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                        const int32_t *roots, int64_t T,
+                        const int32_t *feature, const double *value,
+                        const int32_t *child, const double *leaf, double *out,
+                        void *stream);
+int dkm_rfr_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                        const int32_t *roots, int64_t T,
+                        const int32_t *feature, const double *value,
+                        const int32_t *child, const double *leaf, double *out,
+                        void *stream);
+
+/* ------------------------------------------------------------------------
  * fft (dislib/fft/base.py): batched one-dimensional complex
  * FFT in fp64, X[k] = sum_j x[j] exp(-2 pi i j k / n), for n a power of two
  * up to 2^28, on interleaved complex128 (re, im pairs, 16-byte aligned).
