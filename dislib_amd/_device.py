@@ -1125,6 +1125,93 @@ def tsqr(dd, y, ones, ws=None):
     return R
 
 
+# ---------------------------------------------------------------------------
+# Logistic regression (dkm_logreg.hip)
+# ---------------------------------------------------------------------------
+# the plan of dkm_logreg.hip restated, for the tests to name the branch a
+# shape reaches: rows of a chunk (at least), chunks (at most)
+LOGREG_CHUNK_ROWS = 512
+LOGREG_MAX_CHUNKS = 4096
+
+
+def logreg_tile_rows(d):
+    """Rows of a tile of dkm_logreg_*: 64, 32, 16 for d <= 64, 128, 256."""
+    return 64 if d <= 64 else 32 if d <= 128 else 16
+
+
+def logreg_chunks(n):
+    """Row chunks (workgroups) of dkm_logreg_*; a chunk is whole 64 rows."""
+    return max(1, min((n + LOGREG_CHUNK_ROWS - 1) // LOGREG_CHUNK_ROWS,
+                      LOGREG_MAX_CHUNKS))
+
+
+def logreg_workspace(dd, classes):
+    """The workspace of :func:`logreg_lossgrad` for ``dd`` and ``classes``
+    logit columns; ValueError when it would leave less than 4 GiB of HBM
+    free."""
+    t = torch()
+    nb = int(_lib.lib().dkm_logreg_workspace_bytes(dd.n, dd.d, classes))
+    if nb == 0:
+        raise _lib.DkmError("dkm_logreg_workspace_bytes: bad n/d/classes")
+    free = t.cuda.mem_get_info(dd.device)[0]
+    if nb + _IMAGE_HEADROOM > free:
+        raise ValueError(
+            "LogisticRegression on %d x %d samples: the gradient partials "
+            "need %.2f GiB of HBM, and %.2f GiB are free (4 GiB stay free)"
+            % (dd.n, dd.d, nb / 2.0 ** 30, free / 2.0 ** 30))
+    return _alloc("logreg", nb, lambda: t.empty(nb, dtype=t.uint8,
+                                                device=dd.device))
+
+
+def logreg_lossgrad(dd, y, W, fit_intercept, ws, out):
+    """out (device fp64[1 + W.numel()]) <- [loss | gradient] of the unscaled,
+    unpenalised log-loss at the device fp64 weights ``W`` (logit columns x
+    (d + fit_intercept)), in one read of X (dkm_logreg_lossgrad_*).  ``y``:
+    device int32[n] class indices."""
+    t = torch()
+    so = _lib.lib()
+    fi = int(bool(fit_intercept))
+    if y.dtype != t.int32 or y.numel() != dd.n or not y.is_contiguous():
+        raise ValueError("logreg: y is one contiguous int32 per sample")
+    if W.dtype != t.float64 or W.dim() != 2 or W.shape[1] != dd.d + fi or \
+            not W.is_contiguous() or out.dtype != t.float64 or \
+            out.numel() != 1 + W.numel() or not out.is_contiguous():
+        raise ValueError("logreg: W is fp64 (columns, d + fit_intercept) and "
+                         "out fp64[1 + W.numel()], both contiguous")
+    fn = so.dkm_logreg_lossgrad_f32 if dd.dtype == np.float32 else \
+        so.dkm_logreg_lossgrad_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(y), ptr(W),
+                  int(W.shape[0]), fi, ptr(ws), ws.numel(), ptr(out),
+                  stream_ptr()), "dkm_logreg_lossgrad")
+    return out
+
+
+def logreg_predict(dd, W, fit_intercept, logits=False, proba=False,
+                   labels=False):
+    """(logits, proba, labels) of the rows of ``dd`` at the device fp64
+    weights ``W`` (dkm_logreg_predict_*): fp64 (n, columns) device matrices
+    and int32[n] first-maximum indices, ``None`` where not asked for."""
+    t = torch()
+    so = _lib.lib()
+    fi = int(bool(fit_intercept))
+    if W.dtype != t.float64 or W.dim() != 2 or W.shape[1] != dd.d + fi or \
+            not W.is_contiguous():
+        raise ValueError("logreg: W is contiguous fp64 (columns, d + "
+                         "fit_intercept)")
+    C = int(W.shape[0])
+    Z = t.empty((dd.n, C), dtype=t.float64, device=dd.device) if logits \
+        else None
+    P = t.empty((dd.n, C), dtype=t.float64, device=dd.device) if proba \
+        else None
+    L = t.empty(dd.n, dtype=t.int32, device=dd.device) if labels else None
+    fn = so.dkm_logreg_predict_f32 if dd.dtype == np.float32 else \
+        so.dkm_logreg_predict_f64
+    _lib.check(fn(ptr(dd.X), dd.n, dd.d, dd.X.stride(0), ptr(W), C, fi,
+                  ptr(Z), ptr(P), ptr(L), stream_ptr()),
+               "dkm_logreg_predict")
+    return Z, P, L
+
+
 def add_(y, x, nonzero=None):
     """y += x; with ``nonzero`` (a device int32 element view): 1 there if any
     x != 0, else 0."""

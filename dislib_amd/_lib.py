@@ -29,6 +29,7 @@ RFR_LDS_MAX = 16384
 KPP_MAX_TRIALS = 32
 PCA_MAX_D = 4096
 TSQR_MAX_W = 128
+LOGREG_MAX_D, LOGREG_MAX_CLASSES = 256, 32
 COMM_ID_BYTES = 128
 
 _p = ctypes.c_void_p
@@ -250,6 +251,16 @@ SIGNATURES = {
     "dkm_tsqr_workspace_bytes": (_sz, [_i64, _i64]),
     "dkm_tsqr_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _p, _sz, _p, _p]),
     "dkm_tsqr_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i32, _p, _sz, _p, _p]),
+    # LogisticRegression: [loss | gradient] and the predictions in one pass
+    "dkm_logreg_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "dkm_logreg_lossgrad_f64": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64,
+                                       _i32, _p, _sz, _p, _p]),
+    "dkm_logreg_lossgrad_f32": (_i32, [_p, _i64, _i64, _i64, _p, _p, _i64,
+                                       _i32, _p, _sz, _p, _p]),
+    "dkm_logreg_predict_f64": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32,
+                                      _p, _p, _p, _p]),
+    "dkm_logreg_predict_f32": (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i32,
+                                      _p, _p, _p, _p]),
     # multi-GPU all-reduce (RCCL)
     "dkm_allreduce_unique_id": (_i32, [_p]),
     "dkm_allreduce_init_rank": (_i32, [ctypes.c_char_p, _i32, _i32, _i32]),

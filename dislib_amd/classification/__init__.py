@@ -1,4 +1,5 @@
 from .csvm import CascadeSVM
+from .logreg import LogisticRegression
 from .rf import RandomForestClassifier
 
-__all__ = ["CascadeSVM", "RandomForestClassifier"]
+__all__ = ["CascadeSVM", "LogisticRegression", "RandomForestClassifier"]

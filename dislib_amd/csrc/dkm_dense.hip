@@ -3972,7 +3972,8 @@ int dkm_build_flags(void) {
          tu_flags_ordered() | tu_flags_scale() | tu_flags_gm() |
          tu_flags_dbscan() | tu_flags_als() | tu_flags_svm() |
          tu_flags_rf() | tu_flags_fft() | tu_flags_kpp() |
-         tu_flags_pca() | tu_flags_qr() | tu_flags_rfr();
+         tu_flags_pca() | tu_flags_qr() | tu_flags_rfr() |
+         tu_flags_logreg();
 }
 
 }  // extern "C"

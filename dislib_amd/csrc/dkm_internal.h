@@ -42,6 +42,7 @@ int preload_kpp();
 int preload_pca();
 int preload_qr();
 int preload_rfr();
+int preload_logreg();
 int check_launch(const char *what);
 // Build flags per translation unit (dkm_build_flags ORs them):
 // DKM_BUILD_AB_VARIANT when the file was compiled as an A/B variant
@@ -78,6 +79,7 @@ int tu_flags_kpp();
 int tu_flags_pca();
 int tu_flags_qr();
 int tu_flags_rfr();
+int tu_flags_logreg();
 
 // ---------------------------------------------------------------------------
 // Workspace layout (caller-allocated device memory, carved here).

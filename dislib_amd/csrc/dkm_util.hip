@@ -642,7 +642,7 @@ int dkm_preload(void) {
          preload_ordered() + preload_scale() + preload_gm() +
          preload_dbscan() + preload_als() + preload_svm() + preload_rf() +
          preload_fft() + preload_kpp() + preload_pca() +
-         preload_qr() + preload_rfr();
+         preload_qr() + preload_rfr() + preload_logreg();
   return bad ? fail(DKM_E_LAUNCH, "preload: kernel attribute query") : 0;
 }
 

@@ -1158,6 +1158,55 @@ int dkm_tsqr_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
                  double *R, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Logistic regression (dislib_amd.classification.LogisticRegression,
+ * DESIGN.md 3.27) on dense rows: the unscaled, unpenalised loss and its
+ * gradient, or the logits / probabilities / labels, in ONE read of X.
+ * `classes` is the number of logit columns C, 1 <= C <= DKM_LOGREG_MAX_CLASSES:
+ * C == 1 is the binomial model (y in {0, 1}, loss log(1 + exp(-+z))), C >= 2
+ * the symmetric softmax over C columns (y in [0, C)).  W is a device fp64
+ * matrix of C rows of d + fit_intercept values (the intercept last), y n
+ * int32 device values, n >= 1, 1 <= d <= DKM_LOGREG_MAX_D, ldx >= d.  fp64
+ * arithmetic on the f64 MFMA (fp32 rows are widened in the loads).
+ * Stream-ordered and asynchronous, no floating-point atomic, the same bits
+ * from run to run; DKM_E_ARG for a bad shape or pointer and DKM_E_WORKSPACE
+ * for a short workspace, before any device work.
+ * --------------------------------------------------------------------- */
+#define DKM_LOGREG_MAX_D 256
+#define DKM_LOGREG_MAX_CLASSES 32
+
+/* HOST function: bytes of dkm_logreg_lossgrad_*'s workspace (the row chunks'
+ * loss and gradient partials; the chunks are a function of (n, d)).  0 for a
+ * bad shape. */
+size_t dkm_logreg_workspace_bytes(int64_t n, int64_t d, int64_t classes);
+
+/* out (1 + C (d + fit_intercept) fp64 device values) <- [loss | G]:
+ * loss = sum_i (logsumexp(z_i) - z_i[y_i]) with z_i = W [x_i | 1], and
+ * G (row-major, the shape of W) = sum_i (softmax(z_i) - onehot(y_i)) [x_i | 1]
+ * (C == 1: the binomial loss, and sigmoid(z_i) - y_i in place of the
+ * residual).  Nothing is scaled or penalised. */
+int dkm_logreg_lossgrad_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                            const int32_t *y, const double *W, int64_t classes,
+                            int fit_intercept, void *ws, size_t ws_bytes,
+                            double *out, void *stream);
+int dkm_logreg_lossgrad_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                            const int32_t *y, const double *W, int64_t classes,
+                            int fit_intercept, void *ws, size_t ws_bytes,
+                            double *out, void *stream);
+
+/* Each output may be NULL (not all three): logits (n x C, row-major) <- z;
+ * proba (n x C) <- softmax(z_i) (C == 1: sigmoid(z_i), the probability of
+ * class 1); labels (n int32) <- the first index of the largest logit (C == 1:
+ * z_i > 0). */
+int dkm_logreg_predict_f64(const double *X, int64_t n, int64_t d, int64_t ldx,
+                           const double *W, int64_t classes, int fit_intercept,
+                           double *logits, double *proba, int32_t *labels,
+                           void *stream);
+int dkm_logreg_predict_f32(const float *X, int64_t n, int64_t d, int64_t ldx,
+                           const double *W, int64_t classes, int fit_intercept,
+                           double *logits, double *proba, int32_t *labels,
+                           void *stream);
+
+/* ------------------------------------------------------------------------
  * Dataset loaders.  HOST functions: `buf`
  * and every output are host pointers; no GPU is touched.  `buf` holds
  * the whole file (len bytes); lines end at "\n", "\r\n" or "\r" (Python
